@@ -10,7 +10,11 @@ used only for the timing barrier / max.
 Prints ONE JSON line on rank 0:
   value = first-pass lattice cells of all ranks / max-over-ranks wall time of the K timed steps
   roofline   = region-pass kernel (the dominant kernel) against the HBM roof (MI355X_MICROARCH.md)
-  cpu_baseline = the oracle (oracle/c4_oracle.c, "port") on one pair of the same workload, 1 core
+  cpu_baseline = the oracle (oracle/c4_oracle.c, "port") on one pair of the same workload, 1 core (--full)
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else: staging alone and
+resident, the 512-pair shard, the robustness and both-strands legs, BASELINE's other configurations, the CPU baselines,
+the cross-rank probe and the clock sampler.  --dump-outputs DIR writes the last timed step's results (dump_outputs).
 """
 import argparse
 import json
@@ -332,6 +336,28 @@ def revcomp(seq):
     return seq.translate(bytes.maketrans(b"ACGTacgt", b"TGCAtgca"))[::-1]
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, flat, n):
+    """--dump-outputs: what the last timed step handed its caller (c4gpu_batch_export of this rank's batch), as float64
+    arrays (every value is an int32, exact in float64): valid, score, region (query_start, target_start, query_length,
+    target_length) and n_ops per pair, and ops = the (transition, length) pairs of the valid alignments in pair order.
+    Should the operations not fit in DUMP_LIMIT_BYTES, the pairs are cut to the first ones whose operations do (all arrays)."""
+    import numpy as np
+    flat = np.asarray(flat, dtype=np.int64)
+    head = flat[:7 * n].reshape(n, 7)
+    ops = flat[7 * n:].reshape(-1, 2)
+    ends = np.cumsum(head[:, 6])
+    budget = (DUMP_LIMIT_BYTES - head.size * 8) // 16
+    keep = n if not len(ends) or ends[-1] <= budget else int(np.searchsorted(ends, budget, side="right"))
+    head, ops = head[:keep], ops[:int(ends[keep - 1]) if keep else 0]
+    os.makedirs(d, exist_ok=True)
+    for name, a in (("valid", head[:, 0]), ("score", head[:, 1]), ("region", head[:, 2:6]), ("n_ops", head[:, 6]),
+                    ("ops", ops)):
+        np.save(os.path.join(d, name + ".npy"), a.astype(np.float64))
+
+
 NOMINAL_VALU_G = 0.5 * 1024 * 2.4          # G wave-instructions/s: one wave64 VALU instruction per two cycles and SIMD, 1 024 SIMDs, 2.4 GHz
 
 
@@ -468,6 +494,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-revcomp", action="store_true", help="skip the extra both-strands measurement")
     ap.add_argument("--no-configs", action="store_true", help="skip BASELINE's other configurations (the `configs` block)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: staging alone and resident, shard, robustness, both-strands and "
+                         "configs legs, CPU baselines, cross-rank probe, clock sampling (a plain run times the K steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's batch) as DIR/<name>.npy, float64")
     args = ap.parse_args()
 
     stub = os.environ.get("C4_BENCH_STUB") == "1"
@@ -499,7 +530,7 @@ def main():
                                                 workers=max(1, min(32, cores // max(1, world))))
     # robustness legs (single GPU, full run only): one batch of 1 100-nt cDNAs (five strips of 256 rows: off the staged packed
     # score pass, whose queries must fit the four strips of a workgroup)
-    want_robust = (not stub) and world == 1 and (not args.no_configs) and n_local >= 1024 and args.qlen == 1000
+    want_robust = args.full and (not stub) and world == 1 and (not args.no_configs) and n_local >= 1024 and args.qlen == 1000
     long_q = workloads.est2genome_batches([nb * n_step], n_local, 1100, args.tlen,
                                           workers=max(1, min(32, cores)))[0] if want_robust else None
     # ... and one of 2 048 cDNAs of 2 500 nt (seven strips of 384 rows: two super-strips of the staged form, kpk16j)
@@ -514,7 +545,7 @@ def main():
     # At N > 1 the reference's CPU leg (rank 0, one core, pair 0 of the batch) runs BEFORE the process group exists: the
     # other ranks wait in the rendezvous instead of in a collective; its vulgar line is compared with the GPU's later.
     early_cpu = None
-    if use_dist and rank == 0 and not stub and not args.no_cpu_baseline:
+    if args.full and use_dist and rank == 0 and not stub and not args.no_cpu_baseline:
         early_cpu = reference_one_core(pairs[0])
     if use_dist:
         import torch.distributed as dist
@@ -554,13 +585,13 @@ def main():
     for b in range(min(nb, 2)):
         stage.load(host_batches[b]); batch.swap(stage)
     alone = []
-    for b in range(3):
+    for b in range(3 if args.full else 0):
         sync()
         s0 = time.perf_counter()
         stage.load(host_batches[b % nb])
         sync()
         alone.append(time.perf_counter() - s0)
-    staging_s = sorted(alone)[1]
+    staging_s = sorted(alone)[1] if alone else None
     batch.kernel_stats(MODE_REGION, reset=True)  # switches HIP-event timing of the kernels on
 
     def flush_c_stdio():
@@ -611,6 +642,7 @@ def main():
         fut = loader.submit(stage.load, nxt) if nxt is not None else None
         b.run(2)
         flat = b.export()                                                 # host copy of this rank's results, one stream
+        work["last_flat"] = flat                                          # what the caller receives (--dump-outputs)
         c1 = time.perf_counter()
         if fut is not None:
             fut.result()                                                  # the next batch is resident (normally long since)
@@ -691,17 +723,24 @@ def main():
         work["gathered_ints"] += int(flat.size)
 
     flush_c_stdio()
-    with ClockSampler() as clock_sampler:
+    clock_sampler = ClockSampler() if args.full else None
+    if clock_sampler is not None:
+        with clock_sampler:
+            elapsed = timed(batch, host_batches, args.steps, args.warmup)
+    else:
         elapsed = timed(batch, host_batches, args.steps, args.warmup)
     stats = {m: batch.kernel_stats(m) for m in range(4)}
     ranks_report = dict(per_rank)                                         # of the headline run (the legs below overwrite it)
     headline_work = dict(work)
+    last_flat = work.pop("last_flat", None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_flat, len(host_batches[0]))
 
     # the same steps with the batch resident (what `value` was until round 4): every distinct batch staged, aligned once
     # untimed and once timed, on this rank only; the difference to the streaming step is what staging costs when it runs
     # behind the alignment
     res_ms = []
-    if not use_dist:
+    if args.full and not use_dist:
         for bb in range(min(nb, 4)):
             stage.load(host_batches[bb]); batch.swap(stage)
             batch.run(2)
@@ -714,7 +753,7 @@ def main():
     # BASELINE config 4 as worded ("4 096 cDNAs ... 1 -> 8 MI355X shard-by-query": 512 per GPU at 8): the shard one rank of a
     # strong-scaled 8-GPU run aligns per step, on this GPU alone, streaming like the headline
     shard = None
-    if not stub and not use_dist and not args.no_configs and n_local >= 4096:
+    if args.full and not stub and not use_dist and not args.no_configs and n_local >= 4096:
         shard_batches = [hb[:512] for hb in host_batches]
         keep = dict(work)
         sh_el = timed(batch, shard_batches, 4, 2)
@@ -773,7 +812,7 @@ def main():
     # default (fastapipe.c:42-44): each cDNA and its reverse complement against the same window; the windows are
     # shared buffers, so the device holds each once.  Streaming like the headline; one warm-up + two timed steps.
     rc = None
-    if not args.no_revcomp and not stub:
+    if args.full and not args.no_revcomp and not stub:
         both_batches = []
         for hb in host_batches[:2]:
             both = []
@@ -793,13 +832,15 @@ def main():
         del both_batches
 
     # the checks below read alignments of batch 0 (rank 0: pairs 0 .. of the generator): stage and align it once more
-    stage.load(host_batches[0]); batch.swap(stage); batch.run(2)
-    n_aligned = sum(1 for i in range(min(n_local, 64)) if batch.alignment(i) is not None)
+    n_aligned = None
+    if args.full:
+        stage.load(host_batches[0]); batch.swap(stage); batch.run(2)
+        n_aligned = sum(1 for i in range(min(n_local, 64)) if batch.alignment(i) is not None)
 
     # results compared across ranks: every rank aligns the same probe pair (pair 0 of rank 0's shard) on its own device;
     # the streams must be identical
     probe_same = None
-    if use_dist and not stub:
+    if args.full and use_dist and not stub:
         probe = workloads.est2genome_pairs(1, args.qlen, args.tlen, first=0)
         pb = ex.ResidentBatch(eng, model, probe)
         pb.run(2)
@@ -882,7 +923,7 @@ def main():
         except (OSError, ValueError, KeyError):
             pass
         hidden = None
-        if resident_ms is not None and staging_s > 0:
+        if resident_ms is not None and staging_s:
             hidden = max(0.0, min(1.0, 1.0 - (ms_per_step - resident_ms) / (staging_s * 1e3)))
         out = {
             "metric": "DP cells/s (first-pass lattice cells / end-to-end time), est2genome 1kb x 100kb batch, "
@@ -897,7 +938,8 @@ def main():
             # every timed step stages and aligns a batch it has not seen in the step before: flattening, gather into page-locked
             # memory, PCIe copy, residue coding, splice arrays (the reference's per-pair Sequence_strncpy + splice prediction) are
             # INSIDE `value`, behind the alignment of the batch before (c4gpu_stage)
-            "staging": {"inside_value": True, "ms_alone": staging_s * 1e3, "ms_alone_runs": [x * 1e3 for x in alone],
+            "staging": {"inside_value": True, "ms_alone": staging_s * 1e3 if staging_s is not None else None,
+                        "ms_alone_runs": [x * 1e3 for x in alone],
                         "ms_per_step_resident": resident_ms, "ms_per_step_resident_runs": res_ms,
                         "value_resident": first_pass_cells / (resident_ms * 1e-3) if resident_ms else None,
                         "hidden_frac": hidden, "distinct_batches": nb,
@@ -906,7 +948,7 @@ def main():
                         "note": "hidden_frac = 1 - (ms_per_step - ms_per_step_resident) / ms_alone; ms_per_step_resident: the same "
                                 "batches aligned again while resident (no staging), this rank alone; stage_wait: time a step "
                                 "waited for the next batch's load after its own alignment was done"},
-            "staging_ms": staging_s * 1e3, "staging_hidden_frac": hidden,
+            "staging_ms": staging_s * 1e3 if staging_s is not None else None, "staging_hidden_frac": hidden,
             "config": {"workload": "est2genome (exhaustive Optimal_find_path, -D 32, --revcomp no), %d cDNAs of "
                                    "%d nt x genomic windows of %d nt per GPU and step, a fresh batch every step, shard-by-query"
                                    % (n_local, args.qlen, args.tlen),
@@ -918,7 +960,8 @@ def main():
                                        {"launches_per_step": launches_per_step, "kernel": kname, "valu_pmc": valu_pmc,
                                         "avg_launch_ms": avg_ms, "launches": reg["launches"],
                                         "kernel_cells_per_s": reg["cells"] / (reg["ms"] * 1e-3) if reg["ms"] else 0.0,
-                                        "counters": pmc_note, "clock": clock_sampler.report(),
+                                        "counters": pmc_note,
+                                        "clock": clock_sampler.report() if clock_sampler is not None else {"samples": 0, "note": "--full only"},
                                         "kernels": kernel_table(kernels_pmc, stats, n_local, launches_per_step)}),
             "kernel_ms": {"score": stats[0]["ms"], "region": stats[2]["ms"], "checkpoint": stats[3]["ms"], "path": stats[1]["ms"]},
             # the step as a work-queue step: job header broadcast + work-item scatter + result gather (tensors over RCCL
@@ -934,7 +977,7 @@ def main():
         }
         if rc:
             out["revcomp"] = rc
-        if not args.no_configs and not use_dist and not stub:
+        if args.full and not args.no_configs and not use_dist and not stub:
             out["configs"] = other_configs(ex, eng)
             if shard:
                 shard["frac_of_4096_pair_rate"] = shard["value"] / value
@@ -954,7 +997,11 @@ def main():
             rec["vulgar_identical_to_gpu"] = True
             out["cpu_baseline"] = rec
             out["speedup_vs_cpu_1core"] = value / rec["value"] / world
-        if not args.no_cpu_baseline and not use_dist and not stub:
+        elif args.full and use_dist and not stub and not args.no_cpu_baseline:
+            # no reference binary built here: the CPU restatement on one pair, checked bit-exact against this GPU
+            out["cpu_baseline"] = cpu_baseline(args, rank, model, pairs, batch, eng)
+            out["speedup_vs_cpu_1core"] = value / out["cpu_baseline"]["value"] / world
+        if args.full and not args.no_cpu_baseline and not use_dist and not stub:
             out["cpu_baseline"] = cpu_baseline(args, rank, model, pairs, batch, eng)
             out["speedup_vs_cpu_1core"] = value / out["cpu_baseline"]["value"] / world
             if out["cpu_baseline"]["kind"] == "reference":

@@ -17,7 +17,7 @@ def _run(args, env_extra, timeout=300):
 
 
 def test_gpus_flag_starts_one_rank_per_gpu_and_prints_one_line():
-    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--pairs", "2"], {})
+    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--pairs", "2", "--full"], {})
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
     # exactly one JSON line, and it is the last thing on stdout (the comm library may print a banner before it)
@@ -44,6 +44,22 @@ def test_single_rank_and_launcher_environment():
     # a launcher that disagrees with --gpus is an error, not a silent 1-GPU run
     r = _run(["--gpus", "4", "--steps", "1", "--pairs", "1"], {"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0 and b"--gpus 4" in r.stderr
+
+
+def test_plain_run_times_k_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and leaves the extra legs out; --dump-outputs DIR writes what the
+    last timed step returned (the stub's export: valid 1, score 100, two operations per pair) as float64 arrays."""
+    d = str(tmp_path / "dump")
+    r = _run(["--steps", "4", "--warmup", "1", "--pairs", "3", "--dump-outputs", d], {})
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    out = json.loads(r.stdout.decode().strip().splitlines()[-1])
+    assert out["steps"] == 4 and out["ms_per_step"] > 0 and len(out["ranks"]["rank0_step_ms"]) == 4
+    assert out["staging_ms"] is None and "cpu_baseline" not in out and "configs" not in out
+    import numpy as np
+    arrays = {n: np.load(os.path.join(d, n + ".npy")) for n in ("valid", "score", "region", "n_ops", "ops")}
+    assert all(a.dtype == np.float64 for a in arrays.values())
+    assert arrays["score"].tolist() == [100.0] * 3 and arrays["region"].shape == (3, 4) and arrays["n_ops"].tolist() == [2.0] * 3
+    assert arrays["ops"].tolist() == [[11.0, 5.0], [23.0, 1.0]] * 3
 
 
 def test_strong_scaling_cuts_the_step_into_one_shard_per_rank():

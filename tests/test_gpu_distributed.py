@@ -56,11 +56,25 @@ def test_bench_work_queue_step_on_rccl():
     env = _env()
     env.update(C4_BENCH_FORCE_DIST="1", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--pairs", "64", "--tlen", "50000",
-                        "--no-revcomp"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+                        "--no-revcomp", "--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     out = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])
     wq = out["work_queue"]
     assert "RCCL" in wq["collectives"] and wq["alignments_delivered_per_step"] == 64 and wq["probe_pair_identical_on_all_ranks"] is True
     assert out["n_gpus"] == 1 and out["steps"] == 2
-    # the one-core reference leg ran before the process group was formed and agrees with the GPU's vulgar line
-    assert out["cpu_baseline"]["kind"] == "reference" and out["cpu_baseline"]["vulgar_identical_to_gpu"] is True
+    # the one-core CPU leg agrees with the GPU: the reference binary where the build made it (it ran before the process group
+    # was formed; vulgar line of pair 0), else the CPU restatement (oracle/c4_oracle.c, bit-exact on one pair)
+    if os.path.exists(os.path.join(ROOT, "oracle", "_ref", "exonerate-compiled")):
+        assert out["cpu_baseline"]["kind"] == "reference" and out["cpu_baseline"]["vulgar_identical_to_gpu"] is True
+    else:
+        assert out["cpu_baseline"]["kind"] == "port" and out["cpu_baseline"]["checked_bit_exact_vs_gpu"] is True
+    # pair 0 of the batch on this GPU gives the reference's own vulgar line, as the reference printed it
+    import exonerate_amd as ex
+    from exonerate_amd import workloads
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "bench_rccl_pair0.json")))
+    eng = ex.Engine(0)
+    try:
+        got = eng.find_path(ex.Model("est2genome"), workloads.est2genome_pairs(1, 1000, 50000, first=0))[0]
+        assert got is not None and got.vulgar("qy", "tg") == want["vulgar"]
+    finally:
+        eng.close()

@@ -13,7 +13,7 @@ BENCH="python $ROOT/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-revcomp
 (cd $ROOT && python -c "from exonerate_amd.srchash import csrc_hash; print(csrc_hash())") > "$OUT/csrc_hash.txt"
 cd /tmp
 # (C4GPU_LANES=1 in the environment: the whole round on one launch lane, so that per-kernel times and counters add up to the step)
-python $ROOT/bench.py --steps 2 --warmup 1 ${BENCH_EXTRA:-} > "$OUT/bench.json" 2> "$OUT/bench.err"
+python $ROOT/bench.py --steps 2 --warmup 1 --full ${BENCH_EXTRA:-} > "$OUT/bench.json" 2> "$OUT/bench.err"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python $ROOT/bench.py --no-revcomp --no-configs --no-cpu-baseline > "$OUT/trace.log" 2>&1
 for C in FETCH_SIZE WRITE_SIZE "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAIT_ANY SQ_INSTS_LDS SQ_ACTIVE_INST_LDS"; do
   N=$(echo $C | tr ' ' '_' | cut -c1-24)
