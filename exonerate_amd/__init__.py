@@ -43,13 +43,19 @@ class Model:
     _ALPHABETS = {"est2genome": (0, 0), "protein2dna": (1, 0), "protein2dna:bestfit": (1, 0),
                   "protein2genome": (1, 0), "protein2genome:bestfit": (1, 0)}
 
-    def __init__(self, model_type, query_alphabet=None, target_alphabet=None, params=None):
+    def __init__(self, model_type, query_alphabet=None, target_alphabet=None, params=None, ner_open=None):
+        """ner_open: exonerate's --neropen (model type "ner" only; None = the reference's default, -20)."""
         self.params = params if params is not None else default_params()
         qa, ta = self._ALPHABETS.get(model_type, (ALPHABET_DNA, ALPHABET_DNA))
         qa = qa if query_alphabet is None else query_alphabet
         ta = ta if target_alphabet is None else target_alphabet
         self.c = _abi.Model()
-        if _lib().c4gpu_model_get(model_type.encode(), qa, ta, self.params, self.c) != 0:
+        if ner_open is not None:
+            if model_type != "ner":
+                raise C4GpuError("ner_open only applies to model type 'ner', not %r" % model_type)
+            if _lib().c4gpu_model_get_ner(qa, ta, self.params, int(ner_open), self.c) != 0:
+                raise C4GpuError("unknown or unsupported model type %r" % model_type)
+        elif _lib().c4gpu_model_get(model_type.encode(), qa, ta, self.params, self.c) != 0:
             raise C4GpuError("unknown or unsupported model type %r" % model_type)
         self.model_type = model_type
 

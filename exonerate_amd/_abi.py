@@ -164,6 +164,7 @@ PROTOTYPES = [
     ("c4gpu_params_default", None, [C.POINTER(Params)]),
     ("c4gpu_params_set_forcegtag", None, [C.POINTER(Params), C.c_int]),
     ("c4gpu_model_get", C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(Model)]),
+    ("c4gpu_model_get_ner", C.c_int, [C.c_int, C.c_int, C.POINTER(Params), C.c_int32, C.POINTER(Model)]),
     ("c4gpu_model_get_derived", C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(Params), C.c_int, C.c_int,
                                           C.c_int, C.c_int, C.POINTER(Model), C.POINTER(C.c_int32)]),
     ("c4m_derive", C.c_void_p, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
@@ -271,6 +272,7 @@ PROTOTYPES = [
     ("c4m_flatten", C.c_int, [C.c_void_p, C.POINTER(Model)]),
     ("c4m_ungapped_create", C.c_void_p, [C.c_int, C.c_int, C.POINTER(Params)]),
     ("c4m_affine_create", C.c_void_p, [C.c_int, C.c_int, C.c_int, C.POINTER(Params)]),
+    ("c4m_ner_create", C.c_void_p, [C.c_int, C.c_int, C.POINTER(Params), C.c_int]),
     ("c4m_intron_create", C.c_void_p, [C.c_char_p, C.c_int, C.POINTER(Params)]),
     ("c4m_est2genome_create", C.c_void_p, [C.POINTER(Params)]),
     ("c4m_protein2dna_create", C.c_void_p, [C.c_int, C.POINTER(Params)]),

@@ -58,6 +58,7 @@ int model_family(const c4gpu_model &m) {
     if (model_matches<Protein2GenomePhase1SpanDstDesc>(m)) return FAM_PROTEIN2GENOME_PHASE1_SPAN_DST;
     if (model_matches<Protein2GenomePhase2SpanSrcDesc>(m)) return FAM_PROTEIN2GENOME_PHASE2_SPAN_SRC;
     if (model_matches<Protein2GenomePhase2SpanDstDesc>(m)) return FAM_PROTEIN2GENOME_PHASE2_SPAN_DST;
+    if (model_matches<NerDesc>(m)) return FAM_NER;
     return -1;
 }
 

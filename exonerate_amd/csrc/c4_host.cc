@@ -437,8 +437,11 @@ struct GffCtx {
                     eqfs += t.advance_query * len;
                     etfs += t.advance_target * len;
                     break;
+                case C4GPU_LABEL_NER:                      // the reference aborts here (alignment.c:3104-3105)
+                    c4h::set_error("Unexpected NER for gff gene output");
+                    return -1;
                 default:
-                    return -1;                             // NER: "Unexpected NER for gff gene output"
+                    return -1;
             }
             query_pos += t.advance_query * len;
             target_pos += t.advance_target * len;
@@ -529,6 +532,7 @@ struct ViewCtx {
     std::vector<std::pair<int, int>> row_marker;
     int max_pos_len = 0, width = 0, limit = 0;
     int query_intron_count = 0, target_intron_count = 0, joint_intron_count = 0, intron_aq = 0, intron_at = 0;
+    int ner_count = 0, ner_aq = 0, ner_at = 0;
     char orientation = '.';
     int split_count = 0;
     std::vector<std::pair<int, int>> split_sep;           // (query, target) separation of each split-codon pair
@@ -685,6 +689,20 @@ struct ViewCtx {
         if (last_match->advance_target == 3) add(name, pad.c_str(), middle, pad.c_str(), gap.c_str(), qpos, tpos);
         else add(name, nullptr, middle, nullptr, gap.c_str(), qpos, tpos);
     }
+    void add_ner(int aq, int at, int qpos, int tpos) {                                    // alignment.c:774-812
+        char upper[16], middle[32], lower[16];
+        snprintf(upper, sizeof upper, "%d", aq);
+        snprintf(middle, sizeof middle, "NER %d", ++ner_count);
+        snprintf(lower, sizeof lower, "%d", at);
+        const int max_len = (int)std::max(strlen(upper), std::max(strlen(middle), strlen(lower)));
+        auto padded = [&](const char *text) {
+            const int d = max_len - (int)strlen(text);
+            char out[96];
+            snprintf(out, sizeof out, "--<%*c%s%*c>--", 1 + ((d + 1) >> 1), ' ', text, 1 + (d >> 1), ' ');
+            return std::string(out);
+        };
+        add(padded(upper).c_str(), nullptr, padded(middle).c_str(), nullptr, padded(lower).c_str(), qpos, tpos);
+    }
     void add_split_codon(int aq, int at, int qpos, int tpos) {                            // alignment.c:817-1038, the p,d branch
         if (!q_prot || t_prot || (size_t)(split_count >> 1) >= split_sep.size()) { failed = true; return; }
         const int sep = split_sep[split_count >> 1].second;
@@ -740,7 +758,11 @@ struct ViewCtx {
                 break;
             case C4GPU_LABEL_SPLIT_CODON: add_split_codon(t.advance_query, t.advance_target, qpos, tpos); break;
             case C4GPU_LABEL_FRAMESHIFT: add_frameshift(t.advance_query, t.advance_target, total, qpos, tpos); break;
-            default: failed = true; break;                                                  // NER
+            case C4GPU_LABEL_NER:
+                ner_aq += t.advance_query * total; ner_at += t.advance_target * total;
+                if (!next_same_label) { add_ner(ner_aq, ner_at, qpos, tpos); ner_aq = ner_at = 0; }
+                break;
+            default: failed = true; break;
         }
     }
     int coordinate(bool on_query, bool start) const {                                       // Alignment_get_coordinate, :177-205

@@ -19,6 +19,9 @@ enum Family { FAM_UNGAPPED = 0, FAM_AFFINE, FAM_EST2GENOME, FAM_UNGAPPED_P2D, FA
               FAM_PROTEIN2GENOME_PHASE0_SPAN_SRC, FAM_PROTEIN2GENOME_PHASE0_SPAN_DST,
               FAM_PROTEIN2GENOME_PHASE1_SPAN_SRC, FAM_PROTEIN2GENOME_PHASE1_SPAN_DST,
               FAM_PROTEIN2GENOME_PHASE2_SPAN_SRC, FAM_PROTEIN2GENOME_PHASE2_SPAN_DST,
+              // ner (ner.c:66-114): affine:local plus the non-equivalenced-region state.  Last, so that the families above (and
+              // the ranges family_has_* test) keep their numbers
+              FAM_NER,
               FAM_COUNT };
 
 struct LaunchArgs {

@@ -578,6 +578,23 @@ c4m_model *c4m_affine_create(int type, int qa, int ta, const c4gpu_params *p) {
     return m;
 }
 
+// NER_create, src/model/ner.c:66-114 (the "ner span" of ner.c:105 only feeds the heuristics: not part of c4gpu_model)
+c4m_model *c4m_ner_create(int qa, int ta, const c4gpu_params *p, int ner_open_penalty) {
+    c4m_model *m = c4m_affine_create(C4M_AFFINE_LOCAL, qa, ta, p);
+    if (!m) return nullptr;
+    c4m_model_rename(m, ("NER:" + m->name).c_str());
+    c4m_model_open(m);
+    const int match_state = m->tr[c4m_select_single_transition(m, C4GPU_LABEL_MATCH)].input;
+    int ner = c4m_add_state(m, "ner");
+    int open_c = c4m_add_calc(m, "ner open", C4GPU_CALC_CONST, ner_open_penalty, 0, ner_open_penalty, C4GPU_PROTECT_NONE);
+    c4m_add_transition(m, "match to ner", match_state, ner, 1, 1, open_c, C4GPU_LABEL_NER);
+    c4m_add_transition(m, "ner to match", ner, match_state, 0, 0, -1, C4GPU_LABEL_NONE);
+    c4m_add_transition(m, "ner loop insert", ner, ner, 1, 0, -1, C4GPU_LABEL_NER);
+    c4m_add_transition(m, "ner loop delete", ner, ner, 0, 1, -1, C4GPU_LABEL_NER);
+    c4m_model_close(m);
+    return m;
+}
+
 // Intron_create(suffix, on_query=FALSE, on_target=TRUE, is_forward), src/model/intron.c:497-697
 c4m_model *c4m_intron_create(const char *suffix, int is_forward, const c4gpu_params *p) {
     std::string sfx = suffix;
@@ -714,6 +731,17 @@ int c4gpu_model_get(const char *type, int qa, int ta, const c4gpu_params *params
     return rc;
 }
 
+// NER_create with --neropen (ner.c:31-33)
+int c4gpu_model_get_ner(int qa, int ta, const c4gpu_params *params, int32_t ner_open_penalty, c4gpu_model *out) {
+    c4gpu_params defaults;
+    if (!params) { c4gpu_params_default(&defaults); params = &defaults; }
+    c4m_model *m = c4m_ner_create(qa, ta, params, ner_open_penalty);
+    if (!m) return -1;
+    int rc = c4m_flatten(m, out);
+    c4m_model_destroy(m);
+    return rc;
+}
+
 // C4_DerivedModel_create on a model type: BSDP's join / terminal models (heuristic.c:242-330)
 int c4gpu_model_get_derived(const char *type, int qa, int ta, const c4gpu_params *params, int src_state,
                             int dst_state, int start_scope, int end_scope, c4gpu_model *out,
@@ -747,6 +775,7 @@ static c4m_model *model_of_type(const char *type, int qa, int ta, const c4gpu_pa
     else if (t == "protein2dna:bestfit" || t == "p2d:b") m = c4m_protein2dna_create(C4M_AFFINE_BESTFIT, params);
     else if (t == "protein2genome" || t == "p2g") m = c4m_protein2genome_create(C4M_AFFINE_LOCAL, params);
     else if (t == "protein2genome:bestfit" || t == "p2g:b") m = c4m_protein2genome_create(C4M_AFFINE_BESTFIT, params);
+    else if (t == "ner") m = c4m_ner_create(qa, ta, params, C4GPU_NER_OPEN_DEFAULT);
     return m;
 }
 

@@ -250,9 +250,16 @@ void        c4gpu_params_set_forcegtag(c4gpu_params *params, int on);
 
 /* Model_Type_get_model (modeltype.c): "affine:local", "affine:global", "affine:bestfit",
  * "affine:overlap", "ungapped", "est2genome", "protein2dna", "protein2dna:bestfit", "protein2genome",
- * "protein2genome:bestfit".  Returns 0 on success. */
+ * "protein2genome:bestfit", "ner" (DNA / DNA or protein / protein, NER open penalty C4GPU_NER_OPEN_DEFAULT).
+ * Returns 0 on success. */
 int         c4gpu_model_get(const char *model_type, int query_alphabet, int target_alphabet,
                             const c4gpu_params *params, c4gpu_model *out);
+/* NER_create (src/model/ner.c:66-114) with --neropen: affine:local plus the non-equivalenced-region state, whose opening
+ * transition scores `ner_open_penalty` (the value and max_score of the calc "ner open") and whose two loops score 0.
+ * --minner / --maxner only bound the heuristics' span and have no counterpart here. */
+#define C4GPU_NER_OPEN_DEFAULT (-20)        /* ner.c:31-33 */
+int         c4gpu_model_get_ner(int query_alphabet, int target_alphabet, const c4gpu_params *params,
+                                int32_t ner_open_penalty, c4gpu_model *out);
 /* C4_DerivedModel_create (c4.c:2292-2337) on the model of that type: the closed sub-model of every path from
  * state src_state to state dst_state (state ids of the original model; 0 = START, 1 = END), with the given
  * scopes — BSDP's join models (match state -> match state, CORNER/CORNER, heuristic.c:255) and terminal

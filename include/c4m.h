@@ -72,6 +72,8 @@ int  c4m_flatten(const c4m_model *m, c4gpu_model *out);
 c4m_model *c4m_ungapped_create(int query_alphabet, int target_alphabet, const c4gpu_params *p);  /* ungapped.c:122 */
 c4m_model *c4m_affine_create(int scope_type, int query_alphabet, int target_alphabet,
                              const c4gpu_params *p);                                           /* affine.c:150  */
+c4m_model *c4m_ner_create(int query_alphabet, int target_alphabet, const c4gpu_params *p,
+                          int ner_open_penalty);                                                /* ner.c:66 */
 c4m_model *c4m_intron_create(const char *suffix, int is_forward, const c4gpu_params *p);        /* intron.c:588 (target introns) */
 c4m_model *c4m_est2genome_create(const c4gpu_params *p);                                        /* est2genome.c:58 */
 c4m_model *c4m_protein2dna_create(int scope_type, const c4gpu_params *p);                       /* protein2dna.c:56 */

@@ -322,7 +322,9 @@ gboolean shim_flatten_any(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out, gboo
             else return FALSE;
             if(ud->query->annotation && (!shim_annotation_ok)) return FALSE; /* cds veto, match.c:276-281 */
         } else if((!strcmp(c->name, "gap open")) || (!strcmp(c->name, "gap extend"))
-               || (!strcmp(c->name, "frameshift"))){
+               || (!strcmp(c->name, "frameshift")) || (!strcmp(c->name, "ner open"))){
+            /* "ner open" reads its penalty through the user data: NER_Data begins with Affine_Data, which begins with
+             * Ungapped_Data (ner.h:34-36, affine.h:46-48), so the pointer the model's own calls get is the one passed here */
             o->kind = C4GPU_CALC_CONST;
             o->value = c->calc_func ? c->calc_func(0, 0, ud) : c->max_score;
         } else if(!strncmp(c->name, "5'ss forward", 12)){
@@ -370,6 +372,16 @@ gboolean shim_flatten_any(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out, gboo
             o->dst_transition_mask |= ((uint64_t)1) << ((C4_Transition*)s->dst_transition_list->pdata[j])->id;
         }
     return c4gpu_model_is_accelerated(out);
+    }
+
+gboolean shim_model_has_query_span(C4_Model *m){
+    register guint i;
+    for(i = 0; i < m->span_list->len; i++){
+        register C4_Span *span = m->span_list->pdata[i];
+        if(span->query_loop)
+            return TRUE;
+        }
+    return FALSE;
     }
 
 static gboolean shim_flatten(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out){

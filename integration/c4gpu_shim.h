@@ -19,6 +19,10 @@ void shim_mark(const gchar *what);
 gint shim_batch_size(void);
 /* closed C4_Model -> c4gpu_model; allow_span: BSDP's span models (cell_start_func / cell_end_func become matrices) */
 gboolean shim_flatten_any(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out, gboolean allow_span);
+/* TRUE when some span of the model (C4_Model_add_span) loops on the query axis: the device SDP passes and BSDP's compiled span
+ * families only know spans along the target (introns), so the heuristic seams leave such a model (ner: a span on both axes,
+ * ner.c:105) to the reference's own functions */
+gboolean shim_model_has_query_span(C4_Model *m);
 void shim_params(Ungapped_Data *ud, c4gpu_params *p);
 /* scoring data for calls that have no model at hand (HSP seeding): Match_ArgumentSet's matrices and translation */
 void shim_hsp_params(c4gpu_params *p);

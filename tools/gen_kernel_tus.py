@@ -8,7 +8,7 @@ OUT = os.path.join(ROOT, "exonerate_amd", "csrc", "kernels")
 FAMILIES = [("FAM_UNGAPPED", "UngappedDesc", "ungapped"), ("FAM_AFFINE", "AffineDesc", "affine"),
             ("FAM_EST2GENOME", "Est2GenomeDesc", "est2genome"), ("FAM_UNGAPPED_P2D", "UngappedP2DDesc", "ungapped_p2d"),
             ("FAM_PROTEIN2DNA", "Protein2DnaDesc", "protein2dna"),
-            ("FAM_PROTEIN2GENOME", "Protein2GenomeDesc", "protein2genome")]
+            ("FAM_PROTEIN2GENOME", "Protein2GenomeDesc", "protein2genome"), ("FAM_NER", "NerDesc", "ner")]
 # BSDP's derived models (small CORNER-scoped DPs, thousands per pair): score and quadratic-space path only
 DERIVED = [("FAM_AFFINE_%s", "Affine%sDesc", "affine_%s"), ("FAM_EST2GENOME_FWD_%s", "Est2GenomeFwd%sDesc", "est2genome_fwd_%s"),
            ("FAM_EST2GENOME_REV_%s", "Est2GenomeRev%sDesc", "est2genome_rev_%s"),
@@ -46,7 +46,8 @@ EXPERIMENTS = {}                     # id -> (family, mode, rows per lane, regis
 SEED2_R = {"est2genome": 3}
 SEED2_CAP2 = {}
 SEED2_R2 = {}
-ONLY_LOCAL = {"est2genome"}
+# ner has no non-local form either (ner.c:68)
+ONLY_LOCAL = {"est2genome", "ner"}
 
 os.makedirs(OUT, exist_ok=True)
 _written = set()

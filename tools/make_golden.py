@@ -197,6 +197,80 @@ from golden_util import PARAM_VARIANTS          # the flag lists live next to th
 ALT_FLAGS = PARAM_VARIANTS["altparams"]
 
 
+
+def substitute(rng, s, rate, alphabet):
+    return "".join(rng.choice(alphabet) if rng.random() < rate else ch for ch in s)
+
+
+def ner_pairs(rng, n, alphabet, tag, blocks=(25, 90), long_from=None):
+    """Pairs for the ner model (ner.c): two or three conserved blocks (3-10 % substitutions, every fourth pair with a small
+    indel inside a block) separated by unrelated inserts of DIFFERENT lengths on the two sides (5-60 residues), random flanks.
+    From index long_from on the blocks are long enough for queries of 300 residues and more (two and three strips of query rows)."""
+    cases = []
+    for k in range(n):
+        lo, hi = (110, 200) if (long_from is not None and k >= long_from) else blocks
+        nb = rng.choice([2, 3])
+        q, t = rand_dna(rng, rng.randint(0, 30), alphabet), rand_dna(rng, rng.randint(0, 30), alphabet)
+        for b in range(nb):
+            block = rand_dna(rng, rng.randint(lo, hi), alphabet)
+            copy = substitute(rng, block, rng.uniform(0.03, 0.10), alphabet)
+            if k % 4 == 3 and b == 1:
+                p = rng.randint(8, len(copy) - 8)
+                copy = copy[:p] + (rand_dna(rng, rng.randint(1, 2), alphabet) if rng.random() < 0.5 else "") + copy[p + rng.randint(0, 2):]
+            q += block
+            t += copy
+            if b + 1 < nb:
+                lq = rng.randint(5, 60)
+                lt = rng.choice([x for x in range(5, 61) if x != lq])
+                q += rand_dna(rng, lq, alphabet)
+                t += rand_dna(rng, lt, alphabet)
+        q += rand_dna(rng, rng.randint(0, 30), alphabet)
+        t += rand_dna(rng, rng.randint(0, 30), alphabet)
+        cases.append(("%s%03d" % (tag, k), q, t))
+    return cases
+
+
+REF_EXONERATE = os.path.join(ROOT, "oracle", "_ref", "exonerate")
+NER_CLI_RYO = "ryo: %s %pi %et %em %V\\n"
+# the parameter points of the reference-binary-made ner sets: (alphabet, exonerate flags); the tests turn the flags into a
+# c4gpu_params (golden_util.apply_flags) and --neropen into Model("ner", ner_open=...)
+NER_CLI_SETS = {
+    "ner_cli_default": ("dna", []),
+    "ner_cli_open35": ("dna", ["--neropen", "-35"]),
+    "ner_cli_protein": ("protein", []),
+    "ner_cli_hugegap": ("dna", list(PARAM_VARIANTS["hugegap"])),
+    "ner_cli_hugeopen": ("dna", ["--neropen", "-300000000"]),
+}
+
+
+def run_ner_cli(name):
+    """One JSON per parameter point: the inputs and the stdout lines of the reference binary itself,
+    exonerate --model ner --exhaustive yes --subopt no -n 1 [flags] with every report switched on, one run per pair; the
+    Command line / Hostname / ##date lines (they name the machine and the day) are dropped."""
+    alphabet, flags = NER_CLI_SETS[name]
+    rng = random.Random(6100 + len(name))
+    alpha = AA if alphabet == "protein" else "ACGT"
+    cases = ner_pairs(rng, 3 if name in ("ner_cli_default", "ner_cli_open35") else 2, alpha, "nercli", blocks=(25, 70))
+    out = {"flags": flags, "alphabet": alphabet, "ryo": NER_CLI_RYO, "pairs": []}
+    for cid, q, t in cases:
+        with tempfile.TemporaryDirectory() as d:
+            qf, tf = os.path.join(d, "q.fa"), os.path.join(d, "t.fa")
+            with open(qf, "w") as f:
+                f.write(">%s query of %s\n%s\n" % (cid, name, q))
+            with open(tf, "w") as f:
+                f.write(">tg_%s\n%s\n" % (cid, t))
+            cmd = [REF_EXONERATE, "--model", "ner", "--exhaustive", "yes", "--subopt", "no", "-n", "1"] + flags + \
+                  ["--showalignment", "yes", "--showsugar", "yes", "--showcigar", "yes", "--showvulgar", "yes",
+                   "--showtargetgff", "yes", "--showquerygff", "yes", "--ryo", NER_CLI_RYO, qf, tf]
+            r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, check=True)
+        lines = [l for l in r.stdout.decode().split("\n")
+                 if not l.startswith(("Command line:", "Hostname:", "##date "))]
+        out["pairs"].append({"id": cid, "qdef": "query of %s" % name, "tid": "tg_%s" % cid, "query": q, "target": t, "stdout": lines})
+    with open(os.path.join(OUT, name + ".json"), "w") as f:
+        json.dump(out, f, separators=(",", ":"))
+    print(name, len(out["pairs"]), "pairs,", sum(len(p["stdout"]) for p in out["pairs"]), "lines")
+
+
 def run(model, cases, dpmemory, extra=()):
     # (a case may carry a fourth entry: the query's CDS annotation (cds_start, cds_length) -- exonerate's --annotation)
     with tempfile.NamedTemporaryFile("w", suffix=".tsv", delete=False) as f:
@@ -648,11 +722,27 @@ def main():
     sets.append(("est2genome_annot_D0", "est2genome", annotated([c for c in est if len(c[1]) >= 30 and len(c[2]) >= 13][:12], 42), 0, ()))
     sets.append(("affine_local_dna_annot", "affine:local", annotated([c for c in d if len(c[1]) >= 13 and len(c[2]) >= 13][:14], 43), 32, ()))
     sets.append(("affine_local_dna_annot_D0", "affine:local", annotated([c for c in d if len(c[1]) >= 13 and len(c[2]) >= 13][:12], 44), 0, ()))
+    # ner (ner.c:66-114).  refdump does not register the NER argument set, so its ner open penalty is 0: these sets are the
+    # parameter point --neropen 0 (a NER beats every gap, and the two loops of the ner state tie everywhere: the reference's
+    # tie-break order is pinned by the op ids).  Other penalties come from the reference binary itself (run_ner_cli)
+    nr = random.Random(7311)
+    ner_dna = ner_pairs(nr, 7, "ACGT", "ner", blocks=(25, 60), long_from=4) + repeat_pairs(nr, 3, "dna")
+    ner_prot = ner_pairs(nr, 5, AA, "nerp", blocks=(25, 60), long_from=4)
+    ner_sub = ner_pairs(nr, 1, "ACGT", "nersub", blocks=(25, 50)) + repeat_pairs(nr, 2, "dna")
+    nso = ("--suboptmax", "4", "--suboptthreshold", "30")
+    sets.append(("ner_dna_open0", "ner", ner_dna, 32, ()))
+    sets.append(("ner_protein_open0", "ner:protein", ner_prot, 32, ()))
+    sets.append(("ner_dna_open0_D0", "ner", [c for c in ner_dna if len(c[1]) >= 13 and len(c[2]) >= 13][::2], 0, ()))
+    sets.append(("ner_dna_open0_subopt", "ner", ner_sub, 32, nso))
+    sets.append(("ner_dna_open0_subopt_D0", "ner", ner_sub[:2], 0, nso))
+    for name in sorted(NER_CLI_SETS):
+        if (not only) or name in only:
+            run_ner_cli(name)
     for name, model, cases, dpm, extra in sets:
         if only and name not in only:
             continue
         recs = run(model, cases, dpm, extra)
-        if name.endswith("_subopt_D0"):      # the point sets are those of the -D 32 twin: keep the files small
+        if name.endswith("_subopt_D0") or name.startswith("ner_"):      # the point sets are those of the -D 32 twin (ner: none): keep the files small
             for r in recs:
                 for a in r.get("subopt", []):
                     a.pop("points", None)
