@@ -41,7 +41,9 @@ def default_params():
 class Model:
     """A closed C4 model flattened to tables (c4gpu_model)."""
     _ALPHABETS = {"est2genome": (0, 0), "protein2dna": (1, 0), "protein2dna:bestfit": (1, 0),
-                  "protein2genome": (1, 0), "protein2genome:bestfit": (1, 0)}
+                  "protein2genome": (1, 0), "protein2genome:bestfit": (1, 0),
+                  # both DNA sequences translated, match advance 3/3 (ungapped.c:106-166, coding2coding.c:50-66)
+                  "ungapped:trans": (0, 0), "coding2coding": (0, 0)}
 
     def __init__(self, model_type, query_alphabet=None, target_alphabet=None, params=None, ner_open=None):
         """ner_open: exonerate's --neropen (model type "ner" only; None = the reference's default, -20)."""

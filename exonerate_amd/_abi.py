@@ -22,7 +22,7 @@ MODE_FIND_SCORE, MODE_FIND_PATH, MODE_FIND_REGION, MODE_FIND_CHECKPOINTS = range
 ALPHABET_DNA, ALPHABET_PROTEIN = 0, 1
 SS5_FORWARD, SS3_FORWARD, SS3_REVERSE, SS5_REVERSE = range(4)
 (CALC_CONST, CALC_MATCH_DNA, CALC_MATCH_PROTEIN, CALC_MATCH_P2D, CALC_SPLICE_PRE, CALC_SPLICE_POST,
- CALC_PHASE_PRE, CALC_PHASE_POST) = range(8)
+ CALC_PHASE_PRE, CALC_PHASE_POST, CALC_MATCH_CODON) = range(9)
 
 
 class Calc(C.Structure):
@@ -278,6 +278,7 @@ PROTOTYPES = [
     ("c4m_protein2dna_create", C.c_void_p, [C.c_int, C.POINTER(Params)]),
     ("c4m_phase_create", C.c_void_p, [C.POINTER(Params)]),
     ("c4m_protein2genome_create", C.c_void_p, [C.c_int, C.POINTER(Params)]),
+    ("c4m_coding2coding_create", C.c_void_p, [C.POINTER(Params)]),
 ]
 
 _lib = None

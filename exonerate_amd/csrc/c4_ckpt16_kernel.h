@@ -85,6 +85,7 @@ struct Stage16 {
 template <class M, int R, int ROOT = -1>
 struct WaveCK16 {
     using F = Facts<M>;
+    static_assert(M::MAXAQ == 1, "the packed forms exchange exactly one query row per step");
     using RT = Roots<M>;
     using W32 = WaveDP<M, R, MODE_CKPT, true, true>;
     static constexpr int NS = M::NS, NCOL = M::MAXAT + 1, W = 64 * R, MAXAT = M::MAXAT;

@@ -405,7 +405,7 @@ int c4gpu_batch_viterbi_model(c4gpu_batch *b, const c4gpu_model *model, int mode
             e->model = *model;
             if (e->eng.init(b->ctx, &e->model, &b->params)) return -1;
             // the resident arrays were prepared for the batch's own model: the other model must read the same ones
-            if (family_is_p2d(e->eng.family) != family_is_p2d(b->eng.family) ||
+            if (family_is_p2d(e->eng.family) != family_is_p2d(b->eng.family) || family_is_codon(e->eng.family) != family_is_codon(b->eng.family) ||
                 (family_has_splice(e->eng.family) && !family_has_splice(b->eng.family)) ||
                 (family_has_phase(e->eng.family) && !family_has_phase(b->eng.family))) {
                 c4h::set_error(std::string("model [") + model->name + "] needs sequence arrays this batch was not built with");
@@ -673,6 +673,13 @@ int c4gpu_batch_set_annotation(c4gpu_batch *b, const int32_t *cds_start, const i
             cds[3 * i] = len > 0 ? cds_start[i] : 0; cds[3 * i + 1] = len > 0 ? len : 0; cds[3 * i + 2] = b->seqs.qlen[i];
             any |= len > 0;
         }
+        for (int c = 0; any && c < b->model.n_calcs; c++)
+            if (b->model.calcs[c].kind == C4GPU_CALC_MATCH_CODON) {
+                // Match_3_3_split_score_func vetoes by the frame of the annotated CDS (match.c:513-519): not built
+                c4h::set_error(std::string("c4gpu_batch_set_annotation: model [") + b->model.name +
+                               "] matches translated codons; the frame-dependent annotation veto of the 3:3 match is not supported");
+                return -1;
+            }
         if (any != b->eng.annotated) {
             // the engine's guards and its parameter block follow (Engine::init_host): the veto row armed, the kernels that keep
             // every validity mask, no packed pass, one launch lane (the second lane's engine is built from the same

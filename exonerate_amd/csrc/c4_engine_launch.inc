@@ -149,7 +149,8 @@ struct Engine {
         kp.start_scope = m->start_scope; kp.end_scope = m->end_scope;
         bool protein = false;
         for (int i = 0; i < m->n_calcs; i++)
-            if (m->calcs[i].kind == C4GPU_CALC_MATCH_PROTEIN || m->calcs[i].kind == C4GPU_CALC_MATCH_P2D) protein = true;
+            if (m->calcs[i].kind == C4GPU_CALC_MATCH_PROTEIN || m->calcs[i].kind == C4GPU_CALC_MATCH_P2D ||
+                m->calcs[i].kind == C4GPU_CALC_MATCH_CODON) protein = true;
         memcpy(kp.submat, protein ? &params->protein_submat[0][0] : &params->dna_submat[0][0], sizeof(int) * 24 * 24);
         // --annotation (match.c:276-281): a DNA query position inside its CDS may not take part in a 1:1 DNA match: such
         // positions carry row code 24 (annotate_qcode_kernel), whose row scores MATCH_IMPOSSIBLY_LOW_SCORE against everything

@@ -59,6 +59,8 @@ int model_family(const c4gpu_model &m) {
     if (model_matches<Protein2GenomePhase2SpanSrcDesc>(m)) return FAM_PROTEIN2GENOME_PHASE2_SPAN_SRC;
     if (model_matches<Protein2GenomePhase2SpanDstDesc>(m)) return FAM_PROTEIN2GENOME_PHASE2_SPAN_DST;
     if (model_matches<NerDesc>(m)) return FAM_NER;
+    if (model_matches<UngappedCodonDesc>(m)) return FAM_UNGAPPED_CODON;
+    if (model_matches<Coding2CodingDesc>(m)) return FAM_CODING2CODING;
     return -1;
 }
 
@@ -67,8 +69,11 @@ static bool family_is_p2g_span(int fam) {
 }
 bool family_is_p2d(int fam) {
     return fam == FAM_UNGAPPED_P2D || fam == FAM_PROTEIN2DNA || fam == FAM_PROTEIN2GENOME ||
-           (fam >= FAM_PROTEIN2DNA_START && fam <= FAM_PROTEIN2GENOME_JOIN) || family_is_p2g_span(fam);
+           (fam >= FAM_PROTEIN2DNA_START && fam <= FAM_PROTEIN2GENOME_JOIN) || family_is_p2g_span(fam) ||
+           fam == FAM_UNGAPPED_CODON || fam == FAM_CODING2CODING;
 }
+// both sequences translated (Match_3_3): the query array holds codon row codes too
+bool family_is_codon(int fam) { return fam == FAM_UNGAPPED_CODON || fam == FAM_CODING2CODING; }
 bool family_has_splice(int fam) {
     return fam == FAM_EST2GENOME || fam == FAM_PROTEIN2GENOME || (fam >= FAM_EST2GENOME_FWD_START && fam <= FAM_EST2GENOME_REV_JOIN) ||
            (fam >= FAM_PROTEIN2GENOME_START && fam <= FAM_PROTEIN2GENOME_JOIN) ||
@@ -597,6 +602,9 @@ struct ResidentSeqs {
     int n_utargets = 0;
     DevBuf<long long> d_utoff;
     DevBuf<int> d_utlen;
+    // ... and the unique queries, for the families whose query is translated per sequence (family_is_codon)
+    DevBuf<long long> d_uqoff;
+    DevBuf<int> d_uqlen;
 
     // page-locked staging of the residues, kept between the batches of a c4gpu_stage (build with pin = true)
     PinBuf pin_q, pin_t;
@@ -614,8 +622,8 @@ struct ResidentSeqs {
         total_q = total_t = 0;
         std::map<std::pair<const uint8_t *, int>, long long> qseen, tseen;
         std::vector<int> uq, ut;                      // first pair that holds each unique sequence
-        std::vector<long long> utoff;
-        std::vector<int> utlen;
+        std::vector<long long> utoff, uqoff;          // (uqoff / uqlen: filled for the codon families only)
+        std::vector<int> utlen, uqlen;
         for (int i = 0; i < n; i++) {
             qlen[i] = pairs[i].query_len; tlen[i] = pairs[i].target_len;
             if (qlen[i] < 0 || tlen[i] < 0 || tlen[i] >= (1 << 30) || qlen[i] >= (1 << 30)) {
@@ -702,9 +710,21 @@ struct ResidentSeqs {
         int zero[2] = {0, 0};
         if (bad.upload(zero, 2, s)) return -1;
         const int blocks = 1024;
-        hipLaunchKernelGGL(encode_kernel, dim3(blocks), dim3(256), 0, s, qraw.p, qcode.p, (long long)hq_n, tables.p, bad.p);
-        int max_t = 1;
-        for (int i = 0; i < n; i++) max_t = std::max(max_t, tlen[i]);
+        int max_t = 1, max_q = 1;
+        for (int i = 0; i < n; i++) { max_t = std::max(max_t, tlen[i]); max_q = std::max(max_q, qlen[i]); }
+        if (family_is_codon(family)) {
+            // Match_3_3 (match.c:508-530): the query is translated as the target of protein2dna is -- per position the row of
+            // the residue its codon encodes (same table, same ambiguity handling; the last two positions start no codon).
+            // Once per unique query, as the targets are.
+            uqoff.resize(uq.size()); uqlen.resize(uq.size());
+            for (size_t x = 0; x < uq.size(); x++) { uqoff[x] = qoff[uq[x]]; uqlen[x] = qlen[uq[x]]; }
+            const int nuq = (int)uq.size();
+            if (d_uqoff.upload(uqoff.data(), nuq, s) || d_uqlen.upload(uqlen.data(), nuq, s)) return -1;
+            hipLaunchKernelGGL(codon_kernel, dim3(std::min(256, (max_q + 255) / 256), std::max(1, std::min(nuq, 32768))), dim3(256), 0, s,
+                               qraw.p, qcode.p, d_uqoff.p, d_uqlen.p, nuq, tables.p, bad.p);
+        } else {
+            hipLaunchKernelGGL(encode_kernel, dim3(blocks), dim3(256), 0, s, qraw.p, qcode.p, (long long)hq_n, tables.p, bad.p);
+        }
         const int xb = std::min(256, (max_t + 255) / 256), yb = std::max(1, std::min(n_utargets, 32768));
         if (family_is_p2d(family)) {
             hipLaunchKernelGGL(codon_kernel, dim3(xb, yb), dim3(256), 0, s, traw.p, tcode.p, d_utoff.p, d_utlen.p, n_utargets, tables.p, bad.p);
@@ -787,6 +807,7 @@ struct ResidentSeqs {
         tables.swap(o.tables); splice_models.swap(o.splice_models); bad.swap(o.bad);
         std::swap(dev, o.dev);
         std::swap(n_utargets, o.n_utargets); d_utoff.swap(o.d_utoff); d_utlen.swap(o.d_utlen);
+        d_uqoff.swap(o.d_uqoff); d_uqlen.swap(o.d_uqlen);
         std::swap(pin_q.p, o.pin_q.p); std::swap(pin_q.n, o.pin_q.n); std::swap(pin_t.p, o.pin_t.p); std::swap(pin_t.n, o.pin_t.n);
     }
 };

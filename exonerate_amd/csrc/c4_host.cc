@@ -236,8 +236,10 @@ struct GffCtx {
         if (advance == 1) return (char)s[pos];
         return (char)p->aa[p->trans[p->nt2d[s[pos]] | (p->nt2d[s[pos + 1]] << 4) | (p->nt2d[s[pos + 2]] << 8)]];   // Translate_base
     }
-    // C4_Calc_score of a MATCH transition's calc (match.c:271,287,347)
+    // C4_Calc_score of a MATCH transition's calc (match.c:271,287,347,508)
     int match_score(int qpos, int tpos) const {
+        if (match_kind == C4GPU_CALC_MATCH_CODON)
+            return p->protein_submat[p->submat_index[(uint8_t)symbol(true, qpos, 3)]][p->submat_index[(uint8_t)symbol(false, tpos, 3)]];
         const uint8_t q = r->query[qpos];
         if (match_kind == C4GPU_CALC_MATCH_DNA) return p->dna_submat[p->submat_index[q]][p->submat_index[r->target[tpos]]];
         if (match_kind == C4GPU_CALC_MATCH_PROTEIN) return p->protein_submat[p->submat_index[q]][p->submat_index[r->target[tpos]]];
@@ -489,11 +491,11 @@ extern "C" int c4gpu_alignment_format_gff(const c4gpu_model *m, const c4gpu_para
         const c4gpu_transition &t = m->transitions[k];
         if (t.label != C4GPU_LABEL_MATCH || t.calc < 0) continue;
         const int kind = m->calcs[t.calc].kind;
-        if (kind < C4GPU_CALC_MATCH_DNA || kind > C4GPU_CALC_MATCH_P2D) return INT32_MIN;
+        if ((kind < C4GPU_CALC_MATCH_DNA || kind > C4GPU_CALC_MATCH_P2D) && kind != C4GPU_CALC_MATCH_CODON) return INT32_MIN;
         g.match_kind = kind;
     }
     if (g.match_kind < 0) return INT32_MIN;
-    query_protein = g.match_kind != C4GPU_CALC_MATCH_DNA;
+    query_protein = g.match_kind == C4GPU_CALC_MATCH_PROTEIN || g.match_kind == C4GPU_CALC_MATCH_P2D;
     target_protein = g.match_kind == C4GPU_CALC_MATCH_PROTEIN;
     char today[16];
     const char *date = req->date;
@@ -592,6 +594,17 @@ struct ViewCtx {
         out3[0] = out3[1] = out3[2] = d; out3[3] = 0;
         if (q != t) reverse_translate_marks(q, codon, out3);
     }
+    // Match_3_3_split_display_func (match.c:589-642): the residues' symbol, '+' on a base that differs inside a silent codon
+    // change, '!' on a base that is conserved where the residues differ
+    void codon_display(const char *qc, const char *tc, char *out3) const {
+        const char qa = translate3(qc), ta = translate3(tc);
+        const char d = display_symbol(true, qa, ta);
+        for (int k = 0; k < 3; k++) {
+            const bool same_base = toupper((unsigned char)qc[k]) == toupper((unsigned char)tc[k]);
+            out3[k] = (qa == ta) ? (same_base ? d : '+') : (same_base ? '!' : d);
+        }
+        out3[3] = 0;
+    }
     // Alignment_get_codon_match_string (alignment.c:453-474)
     void codon_match_string(const char *codon, char aa, char *out3) const {
         const char codon_aa = translate3(codon);
@@ -624,7 +637,13 @@ struct ViewCtx {
             const std::string ts = match_string(false, tpos, t.advance_target, max_adv);
             const char *iqs = nullptr, *its = nullptr;
             char ms[4];
-            if (t.advance_target == 3) {
+            if (t.advance_query == 3 && t.advance_target == 3) {
+                const char qcodon[3] = {qsym(qpos), qsym(qpos + 1), qsym(qpos + 2)};
+                const char codon[3] = {tsym(tpos), tsym(tpos + 1), tsym(tpos + 2)};
+                iqs = tla(translate3(qcodon));
+                its = tla(translate3(codon));
+                codon_display(qcodon, codon, ms);                                       // Match_3_3_display_func
+            } else if (t.advance_target == 3) {
                 const char codon[3] = {tsym(tpos), tsym(tpos + 1), tsym(tpos + 2)};
                 its = tla(translate3(codon));
                 p2d_display(qsym(qpos), codon, ms);                                     // Match_1_3_display_func
@@ -828,11 +847,11 @@ extern "C" int c4gpu_alignment_display(const c4gpu_model *m, const c4gpu_params 
         const c4gpu_transition &t = m->transitions[k];
         if (t.label != C4GPU_LABEL_MATCH || t.calc < 0) continue;
         const int kind = m->calcs[t.calc].kind;
-        if (kind < C4GPU_CALC_MATCH_DNA || kind > C4GPU_CALC_MATCH_P2D) return INT32_MIN;
+        if ((kind < C4GPU_CALC_MATCH_DNA || kind > C4GPU_CALC_MATCH_P2D) && kind != C4GPU_CALC_MATCH_CODON) return INT32_MIN;
         v.match_kind = kind;
     }
     if (v.match_kind < 0 || a->n_ops < 1) return INT32_MIN;
-    v.q_prot = v.match_kind != C4GPU_CALC_MATCH_DNA;
+    v.q_prot = v.match_kind == C4GPU_CALC_MATCH_PROTEIN || v.match_kind == C4GPU_CALC_MATCH_P2D;
     v.t_prot = v.match_kind == C4GPU_CALC_MATCH_PROTEIN;
     // AlignmentView_create (alignment.c:285-349)
     v.has_iq = m->max_query_advance == 3;
@@ -946,11 +965,11 @@ extern "C" int c4gpu_alignment_format_ryo(const c4gpu_model *m, const c4gpu_para
         const c4gpu_transition &t = m->transitions[k];
         if (t.label != C4GPU_LABEL_MATCH || t.calc < 0) continue;
         const int kind = m->calcs[t.calc].kind;
-        if (kind < C4GPU_CALC_MATCH_DNA || kind > C4GPU_CALC_MATCH_P2D) return INT32_MIN;
+        if ((kind < C4GPU_CALC_MATCH_DNA || kind > C4GPU_CALC_MATCH_P2D) && kind != C4GPU_CALC_MATCH_CODON) return INT32_MIN;
         g.match_kind = kind;
     }
     if (g.match_kind < 0 || a->n_ops < 1 || !req->format) return INT32_MIN;
-    const bool q_prot = g.match_kind != C4GPU_CALC_MATCH_DNA, t_prot = g.match_kind == C4GPU_CALC_MATCH_PROTEIN;
+    const bool q_prot = g.match_kind == C4GPU_CALC_MATCH_PROTEIN || g.match_kind == C4GPU_CALC_MATCH_P2D, t_prot = g.match_kind == C4GPU_CALC_MATCH_PROTEIN;
     auto coord = [&](bool on_query, int pos) {             // Alignment_convert_coordinate (alignment.c:209-232)
         if (req->forward_coords && (on_query ? req->query_strand : req->target_strand) == '-')
             pos = (on_query ? req->query_len : req->target_len) - pos;
@@ -1127,7 +1146,7 @@ extern "C" int c4gpu_alignment_format_ryo(const c4gpu_model *m, const c4gpu_para
                     else if (c2 == 'i') v = (((float)idm) / ((float)idt)) * 100;
                     else if (c2 == 's') v = (((float)sim) / ((float)simt)) * 100;
                     else if (c2 == 'S') {                   // Alignment_get_percent_self (alignment.c:1563-1618)
-                        if (g.match_kind == C4GPU_CALC_MATCH_P2D) return INT32_MIN;
+                        if (g.match_kind == C4GPU_CALC_MATCH_P2D || g.match_kind == C4GPU_CALC_MATCH_CODON) return INT32_MIN;
                         int score = 0, self = 0, qp = a->region.query_start, tp = a->region.target_start;
                         const bool prot = g.match_kind == C4GPU_CALC_MATCH_PROTEIN;
                         for (int k = 0; k < a->n_ops; k++) {

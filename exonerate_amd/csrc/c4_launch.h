@@ -22,6 +22,9 @@ enum Family { FAM_UNGAPPED = 0, FAM_AFFINE, FAM_EST2GENOME, FAM_UNGAPPED_P2D, FA
               // ner (ner.c:66-114): affine:local plus the non-equivalenced-region state.  Last, so that the families above (and
               // the ranges family_has_* test) keep their numbers
               FAM_NER,
+              // the translated DNA / DNA models, whose match advances 3/3 (max_query_advance = 3: the kernels hand three query
+              // rows from lane to lane): ungapped:trans (ungapped.c:106-166) and coding2coding (coding2coding.c:50-66)
+              FAM_UNGAPPED_CODON, FAM_CODING2CODING,
               FAM_COUNT };
 
 struct LaunchArgs {

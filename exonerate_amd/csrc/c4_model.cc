@@ -176,6 +176,7 @@ const char *match_name(int qa, int ta) {
     if (qa == C4GPU_ALPHABET_DNA && ta == C4GPU_ALPHABET_DNA) return "dna2dna";
     if (qa == C4GPU_ALPHABET_PROTEIN && ta == C4GPU_ALPHABET_PROTEIN) return "protein2protein";
     if (qa == C4GPU_ALPHABET_PROTEIN && ta == C4GPU_ALPHABET_DNA) return "protein2dna";
+    if (qa == C4M_ALPHABET_CODON && ta == C4M_ALPHABET_CODON) return "codon";            // Match_Type_get_name(CODON2CODON)
     return "dna2protein";
 }
 
@@ -523,7 +524,8 @@ int c4m_flatten(const c4m_model *m, c4gpu_model *out) {
 c4m_model *c4m_ungapped_create(int qa, int ta, const c4gpu_params *p) {
     std::string name = std::string("ungapped:") + match_name(qa, ta);
     c4m_model *m = c4m_model_create(name.c_str());
-    c4m_model_set_alphabets(m, qa, ta);
+    const bool codon = qa == C4M_ALPHABET_CODON && ta == C4M_ALPHABET_CODON;      // translate_both: DNA sequences, 3/3 match
+    c4m_model_set_alphabets(m, codon ? C4GPU_ALPHABET_DNA : qa, codon ? C4GPU_ALPHABET_DNA : ta);
     int match_state = c4m_add_state(m, "match");
     int kind, aq = 1, at = 1, mx;
     if (qa == C4GPU_ALPHABET_DNA && ta == C4GPU_ALPHABET_DNA) {
@@ -532,9 +534,11 @@ c4m_model *c4m_ungapped_create(int qa, int ta, const c4gpu_params *p) {
         kind = C4GPU_CALC_MATCH_PROTEIN;  mx = submat_max(p->protein_submat);
     } else if (qa == C4GPU_ALPHABET_PROTEIN && ta == C4GPU_ALPHABET_DNA) {
         kind = C4GPU_CALC_MATCH_P2D;  at = 3;  mx = submat_max(p->protein_submat);
+    } else if (codon) {
+        kind = C4GPU_CALC_MATCH_CODON;  aq = 3;  at = 3;  mx = submat_max(p->protein_submat);
     } else {
         c4m_model_destroy(m);
-        return nullptr;                       // dna2protein / codon2codon: not accelerated
+        return nullptr;                       // dna2protein: not accelerated
     }
     int calc = c4m_add_calc(m, "match", kind, 0, 0, mx, C4GPU_PROTECT_NONE);
     c4m_add_transition(m, "start to match", C4M_START, match_state, 0, 0, -1, C4GPU_LABEL_NONE);
@@ -550,6 +554,8 @@ c4m_model *c4m_affine_create(int type, int qa, int ta, const c4gpu_params *p) {
     static const int type_scope[] = {C4GPU_SCOPE_CORNER, C4GPU_SCOPE_QUERY, C4GPU_SCOPE_ANYWHERE,
                                      C4GPU_SCOPE_EDGE};
     if (type < 0 || type > 3) return nullptr;
+    // translate_both: the reference builds it with the local scope only (coding2coding.c:54); no other scope is served
+    if ((qa == C4M_ALPHABET_CODON || ta == C4M_ALPHABET_CODON) && type != C4M_AFFINE_LOCAL) return nullptr;
     c4m_model *m = c4m_ungapped_create(qa, ta, p);
     if (!m) return nullptr;
     std::string name = std::string("affine:") + type_name[type] + ":" + match_name(qa, ta);
@@ -642,8 +648,9 @@ c4m_model *c4m_est2genome_create(const c4gpu_params *p) {
     return m;
 }
 
-// Frameshift_add(model, match_state, suffix, apply_to_query=FALSE), src/model/frameshift.c:74-131
-static void frameshift_add(c4m_model *m, int match_state, const char *suffix, const c4gpu_params *p) {
+// Frameshift_add(model, match_state, suffix, apply_to_query), src/model/frameshift.c:74-131
+static void frameshift_add(c4m_model *m, int match_state, const char *suffix, const c4gpu_params *p, bool on_query = false) {
+    const int q = on_query ? 1 : 0, t = on_query ? 0 : 1;
     std::string sfx = suffix;
     int fs = c4m_add_state(m, ("frameshift " + sfx).c_str());
     int calc = -1;
@@ -652,10 +659,10 @@ static void frameshift_add(c4m_model *m, int match_state, const char *suffix, co
     if (calc < 0)
         calc = c4m_add_calc(m, "frameshift", C4GPU_CALC_CONST, p->frameshift_penalty, 2,
                             p->frameshift_penalty, C4GPU_PROTECT_NONE);
-    c4m_add_transition(m, ("frameshift open 1 " + sfx).c_str(), match_state, fs, 0, 1, calc, C4GPU_LABEL_FRAMESHIFT);
-    c4m_add_transition(m, ("frameshift open 2 " + sfx).c_str(), match_state, fs, 0, 2, calc, C4GPU_LABEL_FRAMESHIFT);
+    c4m_add_transition(m, ("frameshift open 1 " + sfx).c_str(), match_state, fs, 1 * q, 1 * t, calc, C4GPU_LABEL_FRAMESHIFT);
+    c4m_add_transition(m, ("frameshift open 2 " + sfx).c_str(), match_state, fs, 2 * q, 2 * t, calc, C4GPU_LABEL_FRAMESHIFT);
     c4m_add_transition(m, ("frameshift close 0 " + sfx).c_str(), fs, match_state, 0, 0, -1, C4GPU_LABEL_NONE);
-    c4m_add_transition(m, ("frameshift close 3 " + sfx).c_str(), fs, match_state, 0, 3, -1, C4GPU_LABEL_FRAMESHIFT);
+    c4m_add_transition(m, ("frameshift close 3 " + sfx).c_str(), fs, match_state, 3 * q, 3 * t, -1, C4GPU_LABEL_FRAMESHIFT);
 }
 
 // Protein2DNA_create, src/model/protein2dna.c:56-74
@@ -667,6 +674,20 @@ c4m_model *c4m_protein2dna_create(int type, const c4gpu_params *p) {
     c4m_model_open(m);
     int match_tr = c4m_select_single_transition(m, C4GPU_LABEL_MATCH);
     frameshift_add(m, m->tr[match_tr].input, "p2d", p);
+    c4m_model_close(m);
+    return m;
+}
+
+// Coding2Coding_create, src/model/coding2coding.c:50-66: affine:local over translated codons (the gap calcs then return the
+// codon penalties, affine.c:88-124) with a frameshift state on each axis, both on the one "frameshift" calc
+c4m_model *c4m_coding2coding_create(const c4gpu_params *p) {
+    c4m_model *m = c4m_affine_create(C4M_AFFINE_LOCAL, C4M_ALPHABET_CODON, C4M_ALPHABET_CODON, p);
+    if (!m) return nullptr;
+    c4m_model_rename(m, "coding2coding");
+    c4m_model_open(m);
+    const int match_state = m->tr[c4m_select_single_transition(m, C4GPU_LABEL_MATCH)].input;
+    frameshift_add(m, match_state, "query", p, true);
+    frameshift_add(m, match_state, "target", p, false);
     c4m_model_close(m);
     return m;
 }
@@ -765,6 +786,8 @@ int c4gpu_model_get_derived(const char *type, int qa, int ta, const c4gpu_params
 static c4m_model *model_of_type(const char *type, int qa, int ta, const c4gpu_params *params) {
     c4m_model *m = nullptr;
     std::string t = type;
+    if ((qa != C4GPU_ALPHABET_DNA && qa != C4GPU_ALPHABET_PROTEIN) || (ta != C4GPU_ALPHABET_DNA && ta != C4GPU_ALPHABET_PROTEIN))
+        return nullptr;                       // (the codon pseudo-alphabet of c4m_ungapped_create is not a caller's choice)
     if (t == "ungapped" || t == "u") m = c4m_ungapped_create(qa, ta, params);
     else if (t == "affine:global" || t == "a:g") m = c4m_affine_create(C4M_AFFINE_GLOBAL, qa, ta, params);
     else if (t == "affine:bestfit" || t == "a:b") m = c4m_affine_create(C4M_AFFINE_BESTFIT, qa, ta, params);
@@ -776,6 +799,11 @@ static c4m_model *model_of_type(const char *type, int qa, int ta, const c4gpu_pa
     else if (t == "protein2genome" || t == "p2g") m = c4m_protein2genome_create(C4M_AFFINE_LOCAL, params);
     else if (t == "protein2genome:bestfit" || t == "p2g:b") m = c4m_protein2genome_create(C4M_AFFINE_BESTFIT, params);
     else if (t == "ner") m = c4m_ner_create(qa, ta, params, C4GPU_NER_OPEN_DEFAULT);
+    // the translated models take DNA / DNA only (Model_Type_check_input, modeltype.c)
+    else if ((t == "ungapped:trans" || t == "u:t") && qa == C4GPU_ALPHABET_DNA && ta == C4GPU_ALPHABET_DNA)
+        m = c4m_ungapped_create(C4M_ALPHABET_CODON, C4M_ALPHABET_CODON, params);
+    else if ((t == "coding2coding" || t == "c2c") && qa == C4GPU_ALPHABET_DNA && ta == C4GPU_ALPHABET_DNA)
+        m = c4m_coding2coding_create(params);
     return m;
 }
 
@@ -804,7 +832,7 @@ int c4gpu_model_plugin_name(const c4gpu_model *model, int mode, int use_continua
 
 int c4gpu_model_is_accelerated(const c4gpu_model *model) {
     for (int c = 0; c < model->n_calcs; c++)
-        if (model->calcs[c].kind > C4GPU_CALC_PHASE_POST) return 0;
+        if (model->calcs[c].kind > C4GPU_CALC_MATCH_CODON) return 0;
     for (int s = 0; s < model->n_shadows; s++)
         if (!model->shadows[s].on_target) return 0;
     if (model->total_shadow_designations > 1) return 0;

@@ -103,6 +103,7 @@ struct Dump16 {
 template <class M, int R, int VAR = 0, bool DUMP16 = false, int IO = 0, int NCODE_ = 6, bool MEMC = false>
 struct WaveDP16 {
     using F = Facts<M>;
+    static_assert(M::MAXAQ == 1, "the packed forms exchange exactly one query row per step");
     using W32 = WaveDP<M, R, MODE_SCORE, false, true, false, false, 0, 1>;     // the 32-bit score pass: dump layout
     using D16 = Dump16<M>;
     static constexpr int NS = M::NS, NCOL = M::MAXAT + 1, W = 64 * R, DC = M::MAXAT, SEEDW = DUMP16 ? D16::SEEDW16 : W32::SEEDW;

@@ -40,7 +40,9 @@ constexpr int CELL_MAX = 8;
 enum { MODE_SCORE = 0, MODE_PATH = 1, MODE_REGION = 2, MODE_CKPT = 3 };
 enum { SCOPE_ANYWHERE = 0, SCOPE_EDGE, SCOPE_QUERY, SCOPE_TARGET, SCOPE_CORNER };
 enum { CALC_CONST = 0, CALC_MATCH_DNA, CALC_MATCH_PROTEIN, CALC_MATCH_P2D, CALC_SPLICE_PRE, CALC_SPLICE_POST,
-       CALC_PHASE_PRE, CALC_PHASE_POST };
+       CALC_PHASE_PRE, CALC_PHASE_POST, CALC_MATCH_CODON };
+// a substitution-matrix lookup of (query row code, target column code): 1:1 residues, 1:3 and 3:3 translated codons
+constexpr bool calc_is_match(int kind) { return (kind >= CALC_MATCH_DNA && kind <= CALC_MATCH_P2D) || kind == CALC_MATCH_CODON; }
 enum { FLAG_OPS_OVERFLOW = 1, FLAG_NO_END = 2 };
 enum { LABEL_NONE = 0, LABEL_MATCH = 1 };            // C4_Label, c4.h:78-89
 
@@ -142,7 +144,9 @@ struct Facts {
     static constexpr int n_exported() { int n = 0; for (int s = 0; s < M::NS; s++) n += exported(s); return n; }
     static constexpr bool owns_shadow(int s, int d) { for (int h = 0; h < M::NSH; h++) if (M::sh[h].designation == d && (M::sh[h].src_state_mask >> s & 1)) return true; return false; }
     static constexpr int consumed_designation(int k) { for (int h = 0; h < M::NSH; h++) if (M::tr[k].dst_shadow_mask >> h & 1) return M::sh[h].designation; return -1; }
-    static constexpr int match_at() { for (int k = 0; k < M::NT; k++) if (M::tr[k].calc >= 0 && M::calc[M::tr[k].calc].kind >= CALC_MATCH_DNA && M::calc[M::tr[k].calc].kind <= CALC_MATCH_P2D) return M::tr[k].at; return 1; }
+    static constexpr int match_at() { for (int k = 0; k < M::NT; k++) if (M::tr[k].calc >= 0 && calc_is_match(M::calc[M::tr[k].calc].kind)) return M::tr[k].at; return 1; }
+    // query rows the match transition consumes: its row code is that of the residue (codon) starting match_aq() rows above
+    static constexpr int match_aq() { for (int k = 0; k < M::NT; k++) if (M::tr[k].calc >= 0 && calc_is_match(M::calc[M::tr[k].calc].kind)) return M::tr[k].aq; return 1; }
     static constexpr bool has_phase() { for (int c = 0; c < M::NC; c++) if (M::calc[c].kind == CALC_PHASE_POST) return true; return false; }
     static constexpr bool has_splice() { for (int c = 0; c < M::NC; c++) if (M::calc[c].kind == CALC_SPLICE_PRE || M::calc[c].kind == CALC_SPLICE_POST) return true; return false; }
     // every state a MATCH-labelled transition enters also has a silent, calc-free transition from START (score 0
@@ -159,7 +163,7 @@ struct Facts {
         }
         return true;
     }
-    static_assert(M::MAXAQ == 1, "lanes exchange exactly one query row per step");
+    static_assert(M::MAXAQ >= 1 && M::MAXAQ <= 3, "lanes exchange the last MAXAQ query rows per step (WaveDP::AQ)");
     static_assert(total_bits <= 32, "traceback word");
 };
 
@@ -279,9 +283,15 @@ struct WaveDP {
     static constexpr int W = 64 * R;                    // query rows per strip
     static constexpr int NCOL = M::MAXAT + 1;           // live columns, kept as a ring (no register rotation)
     static constexpr int NEXP = F::n_exported();
+    // A transition that advances the query by a reads row i - a: sub-row RR - a of the same lane where RR >= a, else sub-row
+    // R + RR - a of the lane above.  So a lane hands its LAST AQ sub-rows down (nbr, expo, the carry row between strips and the
+    // empty column all hold AQ rows per exported state; row k of them is sub-row R - AQ + k), and needs R >= AQ rows of its own.
+    static constexpr int AQ = M::MAXAQ;
+    static_assert(R >= AQ, "a lane hands its last MAXAQ rows down: it needs that many");
     // sub-optimal blocking in the local score / region passes: see eval_cell
     static constexpr bool BLOCK_AS_LOW = LOCAL && (MODE == MODE_SCORE || MODE == MODE_REGION) && F::match_states_have_start();
-    static constexpr int BND = NEXP * (1 + XS);         // ints per column in the strip carry row
+    static constexpr int BND1 = NEXP * (1 + XS);        // ints per column and carried row
+    static constexpr int BND = BND1 * AQ;               // ints per column in the strip carry row
     static constexpr int XD = NDES + NAUX;              // shadow-like slots of a dumped cell
     static constexpr int DC = M::MAXAT;                 // columns per dump: d*K - (DC - 1) .. d*K
     static_assert(SEED == 0 || (SEED == 1 && MODE == MODE_SCORE) || (SEED == 2 && MODE == MODE_REGION && PACK),
@@ -348,8 +358,8 @@ struct WaveDP {
     int start_scope, end_scope;
 
     // per-lane DP state: col[p] = the R cells evaluated at the step with phase p = s % NCOL,
-    // nbr[p] = the cell above them (row i0-1 of that column), expo = our bottom row for the lane below
-    C col[NCOL][R], nbr[NCOL], expo;
+    // nbr[p] = the AQ cells above them (rows i0-AQ .. i0-1 of that column), expo = our bottom AQ rows for the lane below
+    C col[NCOL][R], nbr[NCOL][AQ], expo[AQ];
     int qcode[R];
     int best, best_i, best_j, best_qs, best_ts;
     bool best_set;
@@ -417,6 +427,8 @@ struct WaveDP {
         // to the corner can visit has a candidate of real magnitude and takes it (first valid transition assigns, later
         // ones replace on strict <: both forms pick the same transition among the real candidates, in the same order).
         // The host only picks these kernels while that bound keeps the two ranges apart (Engine::cont_free_ok).
+        // A transition that advances the query by a > 1 needs i - a >= 0 (i_ok is the case a = 1); the shortcut's phantom rows
+        // are then the a rows above row 0, all of them the empty column.
         const bool i_ok = (RR > 0) | (i > 0) | (LOCAL && (CONT || MODE == MODE_SCORE || MODE == MODE_REGION));
         uint32_t tbw = 0;
         static_for<M::NT>([&](auto K_) __attribute__((always_inline)) { constexpr int K = K_;
@@ -430,7 +442,8 @@ struct WaveDP {
             if constexpr (!tr_alive(k) && !(CONT && t.in == M::START)) return;
             // Layout_transition_is_valid (layout.c:122-154)
             bool valid = true;
-            if constexpr (t.aq > 0) valid = valid & i_ok;
+            if constexpr (t.aq == 1) valid = valid & i_ok;
+            if constexpr (t.aq > 1) valid = valid & ((RR >= t.aq) | (i > t.aq - 1) | (LOCAL && (CONT || MODE == MODE_SCORE || MODE == MODE_REGION)));
             if constexpr (t.at > 0 && !JINT) valid = valid & (j >= t.at);
             if constexpr (t.in == M::START && (!LOCAL || CONT))
                 valid = valid & (CONT ? ((i - t.aq == 0) & (j - t.at == 0))
@@ -477,7 +490,8 @@ struct WaveDP {
             if constexpr (!tr_alive(k)) return;                  // (COMP: seeded above where it is a transition out of START)
             // source cell: same cell (silent), row above (lane-local or the neighbour's), earlier columns
             constexpr int PD = (PH - t.at + NCOL) % NCOL;
-            const C &cell_src = (t.aq == 0) ? col[PD][RR] : (RR > 0 ? col[PD][RR > 0 ? RR - 1 : 0] : nbr[PD]);
+            const C &cell_src = (t.aq == 0) ? col[PD][RR]
+                              : (RR >= t.aq ? col[PD][RR >= t.aq ? RR - t.aq : 0] : nbr[PD][RR >= t.aq ? 0 : RR - t.aq + AQ]);
             // cell_start_func (viterbi.c:728-741): the START cell of position (i - aq, j - at) comes from the
             // job's matrix, score and shadow slots (clamped, unconditional loads; invalid transitions ignore them)
             C start_cell;
@@ -504,7 +518,7 @@ struct WaveDP {
                 constexpr CalcDesc cd = M::calc[t.calc];
                 if constexpr (cd.kind == CALC_CONST) {
                     tscore += kp->calc_value[t.calc];
-                } else if constexpr (cd.kind >= CALC_MATCH_DNA && cd.kind <= CALC_MATCH_P2D) {
+                } else if constexpr (calc_is_match(cd.kind)) {
                     tscore += mscore;
                 } else if constexpr (cd.kind == CALC_SPLICE_PRE) {
                     tscore += pre[cd.param];             // open penalty + ss[param][tpos], hoisted per column
@@ -613,11 +627,18 @@ struct WaveDP {
             }
         });
     }
+    // ... per carried row K (row K of a column's carry entry starts BND1 ints after row K - 1)
+    template <class Fn>
+    __device__ __forceinline__ static void for_exported_rows(Fn &&fn) {
+        static_for<AQ>([&](auto K_) __attribute__((always_inline)) {
+            for_exported([&](auto S_, int slot) __attribute__((always_inline)) { fn(K_, S_, decltype(K_)::value * BND1 + slot); });
+        });
+    }
 
     // lane 0's neighbour row comes from the carry row the previous strip wrote.  Lane 0 is at column
     // j = s, so every lane requests the same (clamped) column one step ahead: an unconditional, uniform
     // load with no dependent ALU op, so nothing waits for it until the next step's DPP exchange.
-    C nx_carry;
+    C nx_carry[AQ];
     static constexpr int RING = 256;                    // columns of an LDS carry ring (multi-wave kernels)
     typedef __attribute__((address_space(3))) int lds_int;
     lds_int *ring_in, *ring_out;
@@ -629,7 +650,7 @@ struct WaveDP {
     // The first strip has no row above it: its lane 0 reads an "empty" column (every state unset: -987654321,
     // slots 0) through the same prefetch as a real carry row, so the step needs no first-strip selects.
     __device__ __forceinline__ static void write_empty_column(int *col) {
-        for_exported([&](auto S_, int slot) __attribute__((always_inline)) {
+        for_exported_rows([&](auto K_, auto S_, int slot) __attribute__((always_inline)) {
             col[slot] = LOW;
             static_for<XS>([&](auto E_) __attribute__((always_inline)) { constexpr int E = E_; col[slot + 1 + E] = 0; });
         });
@@ -638,19 +659,19 @@ struct WaveDP {
         const int jx = s_next < 0 ? 0 : (s_next > T ? T : s_next);
         const int jc = (carry_cols | use_ring_in) ? jx : 0;    // no row above / no carry rows: every load hits column 0
         if (use_ring_in) {
-            for_exported([&](auto S_, int slot) __attribute__((always_inline)) { constexpr int S = S_;
+            for_exported_rows([&](auto K_, auto S_, int slot) __attribute__((always_inline)) { constexpr int S = S_; constexpr int K = K_;
                 const lds_int *p = ring_in + (jc & (RING - 1)) * BND + slot;
-                nx_carry.sc[S] = p[0];
+                nx_carry[K].sc[S] = p[0];
                 static_for<XS>([&](auto E_) __attribute__((always_inline)) { constexpr int E = E_;
-                    if constexpr (X > 0) if constexpr (slot_live(S, E)) nx_carry.ex[S][E] = p[1 + E];
+                    if constexpr (X > 0) if constexpr (slot_live(S, E)) nx_carry[K].ex[S][E] = p[1 + E];
                 });
             });
         } else {
-            for_exported([&](auto S_, int slot) __attribute__((always_inline)) { constexpr int S = S_;
+            for_exported_rows([&](auto K_, auto S_, int slot) __attribute__((always_inline)) { constexpr int S = S_; constexpr int K = K_;
                 const int *p = bnd_in + (long long)jc * BND + slot;
-                nx_carry.sc[S] = p[0];
+                nx_carry[K].sc[S] = p[0];
                 static_for<XS>([&](auto E_) __attribute__((always_inline)) { constexpr int E = E_;
-                    if constexpr (X > 0) if constexpr (slot_live(S, E)) nx_carry.ex[S][E] = p[1 + E];
+                    if constexpr (X > 0) if constexpr (slot_live(S, E)) nx_carry[K].ex[S][E] = p[1 + E];
                 });
             });
         }
@@ -786,15 +807,15 @@ struct WaveDP {
                 if constexpr (cd.kind == CALC_SPLICE_POST) sp[cd.param] = nx_sp[cd.param];
             });
         }
-        // (1) row i0-1 of this column: from lane-1 (DPP) or, for lane 0, from the previous strip's carry row
+        // (1) rows i0-AQ .. i0-1 of this column: from lane-1 (DPP) or, for lane 0, from the previous strip's carry row
         // (requested one step ago)
-        for_exported([&](auto S_, int slot) __attribute__((always_inline)) { constexpr int S = S_;
-            const int c_sc = nx_carry.sc[S];
-            nbr[PH].sc[S] = dpp_shr1(c_sc, expo.sc[S]);        // first strip: the carry source is the empty column
+        for_exported_rows([&](auto K_, auto S_, int slot) __attribute__((always_inline)) { constexpr int S = S_; constexpr int K = K_;
+            const int c_sc = nx_carry[K].sc[S];
+            nbr[PH][K].sc[S] = dpp_shr1(c_sc, expo[K].sc[S]);  // first strip: the carry source is the empty column
             static_for<XS>([&](auto E_) __attribute__((always_inline)) { constexpr int E = E_;
                 if constexpr (X > 0) if constexpr (slot_live(S, E)) {
-                    const int c_ex = nx_carry.ex[S][E];
-                    nbr[PH].ex[S][E] = dpp_shr1(c_ex, expo.ex[S][E]);
+                    const int c_ex = nx_carry[K].ex[S][E];
+                    nbr[PH][K].ex[S][E] = dpp_shr1(c_ex, expo[K].ex[S][E]);
                 }
             });
         });
@@ -860,28 +881,28 @@ struct WaveDP {
             uint32_t *p = tb_slab + tb_base + ((long long)s * 64 + lane) * R;
             if (jact) static_for<R>([&](auto RR_) __attribute__((always_inline)) { constexpr int RR = RR_; p[RR] = tbw[RR]; });
         }
-        // (5) export the bottom row BEFORE any checkpoint edit (the next lane still needs column j as it was)
-        for_exported([&](auto S_, int) __attribute__((always_inline)) { constexpr int S = S_;
-            expo.sc[S] = col[PH][R - 1].sc[S];
+        // (5) export the bottom AQ rows BEFORE any checkpoint edit (the next lane still needs column j as it was)
+        for_exported_rows([&](auto K_, auto S_, int) __attribute__((always_inline)) { constexpr int S = S_; constexpr int K = K_;
+            expo[K].sc[S] = col[PH][R - AQ + K].sc[S];
             static_for<XS>([&](auto E_) __attribute__((always_inline)) { constexpr int E = E_;
-                if constexpr (X > 0) if constexpr (slot_live(S, E)) expo.ex[S][E] = col[PH][R - 1].ex[S][E];
+                if constexpr (X > 0) if constexpr (slot_live(S, E)) expo[K].ex[S][E] = col[PH][R - AQ + K].ex[S][E];
             });
         });
         if (!last_strip && lane == 63 && jact) {
             if (use_ring_out) {
-                for_exported([&](auto S_, int slot) __attribute__((always_inline)) { constexpr int S = S_;
+                for_exported_rows([&](auto K_, auto S_, int slot) __attribute__((always_inline)) { constexpr int S = S_; constexpr int K = K_;
                     lds_int *p = ring_out + (j & (RING - 1)) * BND + slot;
-                    p[0] = expo.sc[S];
+                    p[0] = expo[K].sc[S];
                     static_for<XS>([&](auto E_) __attribute__((always_inline)) { constexpr int E = E_;
-                        if constexpr (X > 0) if constexpr (slot_live(S, E)) p[1 + E] = expo.ex[S][E];
+                        if constexpr (X > 0) if constexpr (slot_live(S, E)) p[1 + E] = expo[K].ex[S][E];
                     });
                 });
             } else {
-                for_exported([&](auto S_, int slot) __attribute__((always_inline)) { constexpr int S = S_;
+                for_exported_rows([&](auto K_, auto S_, int slot) __attribute__((always_inline)) { constexpr int S = S_; constexpr int K = K_;
                     int *p = bnd_out + (long long)j * BND + slot;
-                    p[0] = expo.sc[S];
+                    p[0] = expo[K].sc[S];
                     static_for<XS>([&](auto E_) __attribute__((always_inline)) { constexpr int E = E_;
-                        if constexpr (X > 0) if constexpr (slot_live(S, E)) p[1 + E] = expo.ex[S][E];
+                        if constexpr (X > 0) if constexpr (slot_live(S, E)) p[1 + E] = expo[K].ex[S][E];
                     });
                 });
             }
@@ -981,9 +1002,11 @@ struct WaveDP {
                             col[PR][RR].ex[S][SRP] = ((i * M::NS) + S) * M::MAXAT + ROW;     // viterbi.c:515-522
                         });
                     });
-                    // our copies of row i0-1 at these columns get the same edit
-                    static_for<M::NS>([&](auto S_) __attribute__((always_inline)) { constexpr int S = S_;
-                        nbr[PR].ex[S][SRP] = (((i0v - 1) * M::NS) + S) * M::MAXAT + ROW;
+                    // our copies of rows i0-AQ .. i0-1 at these columns get the same edit
+                    static_for<AQ>([&](auto K_) __attribute__((always_inline)) { constexpr int K = K_;
+                        static_for<M::NS>([&](auto S_) __attribute__((always_inline)) { constexpr int S = S_;
+                            nbr[PR][K].ex[S][SRP] = (((i0v - AQ + K) * M::NS) + S) * M::MAXAT + ROW;
+                        });
                     });
                 });
                 cp_next_i += 1; cp_next_j += section_length;
@@ -1028,16 +1051,21 @@ struct WaveDP {
         for (int b = 0; b < nstrips; b++) {
             const int i0 = b * W + lane * R;
             static_for<R>([&](auto RR_) __attribute__((always_inline)) { constexpr int RR = RR_;
-                const int qpos = q0 + i0 + RR - 1;            // residue consumed by an advance_query=1 move into row i
-                qcode[RR] = (i0 + RR >= 1 && i0 + RR <= Q) ? qc[qpos] : 0;
+                constexpr int MQ = F::match_aq();
+                const int qpos = q0 + i0 + RR - MQ;           // residue (codon start) consumed by the match move into row i
+                qcode[RR] = (i0 + RR >= MQ && i0 + RR <= Q) ? qc[qpos] : 0;
             });
             // registers start empty (row -1 does not exist; validity masks keep it unread)
             static_for<M::NS>([&](auto S_) __attribute__((always_inline)) { constexpr int S = S_;
-                expo.sc[S] = LOW;
-                static_for<XS>([&](auto E_) __attribute__((always_inline)) { constexpr int E = E_; expo.ex[S][E] = 0; });
+                static_for<AQ>([&](auto K_) __attribute__((always_inline)) { constexpr int K = K_;
+                    expo[K].sc[S] = LOW;
+                    static_for<XS>([&](auto E_) __attribute__((always_inline)) { constexpr int E = E_; expo[K].ex[S][E] = 0; });
+                });
                 static_for<NCOL>([&](auto D_) __attribute__((always_inline)) { constexpr int D = D_;
-                    nbr[D].sc[S] = LOW;
-                    static_for<XS>([&](auto E_) __attribute__((always_inline)) { constexpr int E = E_; nbr[D].ex[S][E] = 0; });
+                    static_for<AQ>([&](auto K_) __attribute__((always_inline)) { constexpr int K = K_;
+                        nbr[D][K].sc[S] = LOW;
+                        static_for<XS>([&](auto E_) __attribute__((always_inline)) { constexpr int E = E_; nbr[D][K].ex[S][E] = 0; });
+                    });
                     static_for<R>([&](auto RR_) __attribute__((always_inline)) { constexpr int RR = RR_;
                         col[D][RR].sc[S] = LOW;
                         static_for<XS>([&](auto E_) __attribute__((always_inline)) { constexpr int E = E_; col[D][RR].ex[S][E] = 0; });
@@ -1091,6 +1119,7 @@ struct WaveDP {
         constexpr bool STG = STG_;
         static_assert(STG_CH == CH, "the stage is sized for run_mw's chunk");
         static_assert(!CONT && (MODE == MODE_SCORE || MODE == MODE_REGION), "multi-wave: full-rectangle passes");
+        static_assert(M::MAXAQ == 1, "the cooperating-wave form exchanges exactly one query row per step");
         Q = job.Q; T = job.T; q0 = job.q0; t0 = job.t0;
         tshift = job.tshift;
         tlast = seqs.tlen[job.pair] > 0 ? seqs.tlen[job.pair] - 1 : 0;
@@ -1132,11 +1161,15 @@ struct WaveDP {
                 qcode[RR] = (i0 + RR >= 1 && i0 + RR <= Q) ? qc[qpos] : 0;
             });
             static_for<M::NS>([&](auto S_) __attribute__((always_inline)) { constexpr int S = S_;
-                expo.sc[S] = LOW;
-                static_for<XS>([&](auto E_) __attribute__((always_inline)) { constexpr int E = E_; expo.ex[S][E] = 0; });
+                static_for<AQ>([&](auto K_) __attribute__((always_inline)) { constexpr int K = K_;
+                    expo[K].sc[S] = LOW;
+                    static_for<XS>([&](auto E_) __attribute__((always_inline)) { constexpr int E = E_; expo[K].ex[S][E] = 0; });
+                });
                 static_for<NCOL>([&](auto D_) __attribute__((always_inline)) { constexpr int D = D_;
-                    nbr[D].sc[S] = LOW;
-                    static_for<XS>([&](auto E_) __attribute__((always_inline)) { constexpr int E = E_; nbr[D].ex[S][E] = 0; });
+                    static_for<AQ>([&](auto K_) __attribute__((always_inline)) { constexpr int K = K_;
+                        nbr[D][K].sc[S] = LOW;
+                        static_for<XS>([&](auto E_) __attribute__((always_inline)) { constexpr int E = E_; nbr[D][K].ex[S][E] = 0; });
+                    });
                     static_for<R>([&](auto RR_) __attribute__((always_inline)) { constexpr int RR = RR_;
                         col[D][RR].sc[S] = LOW;
                         static_for<XS>([&](auto E_) __attribute__((always_inline)) { constexpr int E = E_; col[D][RR].ex[S][E] = 0; });

@@ -37,6 +37,7 @@ namespace c4k {
 template <class M, int R, int ROOT>
 struct WaveWin16 {
     using F = Facts<M>;
+    static_assert(M::MAXAQ == 1, "the packed forms exchange exactly one query row per step");
     using D16 = Dump16<M>;
     using RT = Roots<M>;
     static constexpr int NS = M::NS, NCOL = M::MAXAT + 1, W = 64 * R, MAXAT = M::MAXAT, DC = M::MAXAT;

@@ -68,7 +68,8 @@ enum {
     C4GPU_CALC_SPLICE_PRE,       /* Intron_calc_* with is_pre     intron.c:138-161: value + ss[param][tpos]  */
     C4GPU_CALC_SPLICE_POST,      /* Intron_calc_* post: length check against shadow, then ss[param][tpos]    */
     C4GPU_CALC_PHASE_PRE,        /* phase.c split-codon calcs (protein2genome)                               */
-    C4GPU_CALC_PHASE_POST
+    C4GPU_CALC_PHASE_POST,
+    C4GPU_CALC_MATCH_CODON       /* Match_3_3_split_score_func    match.c:508  protein submat[aa(q..q+2)][aa(t..t+2)] */
 };
 
 /* C4_Calc, src/c4/c4.h:75-86 */
@@ -250,7 +251,9 @@ void        c4gpu_params_set_forcegtag(c4gpu_params *params, int on);
 
 /* Model_Type_get_model (modeltype.c): "affine:local", "affine:global", "affine:bestfit",
  * "affine:overlap", "ungapped", "est2genome", "protein2dna", "protein2dna:bestfit", "protein2genome",
- * "protein2genome:bestfit", "ner" (DNA / DNA or protein / protein, NER open penalty C4GPU_NER_OPEN_DEFAULT).
+ * "protein2genome:bestfit", "ner" (DNA / DNA or protein / protein, NER open penalty C4GPU_NER_OPEN_DEFAULT),
+ * "ungapped:trans" (Ungapped_create(CODON2CODON), named "ungapped:codon") and "coding2coding" (coding2coding.c:50-66):
+ * DNA / DNA with both sequences translated, match advance 3/3, max_query_advance = 3.
  * Returns 0 on success. */
 int         c4gpu_model_get(const char *model_type, int query_alphabet, int target_alphabet,
                             const c4gpu_params *params, c4gpu_model *out);
@@ -377,7 +380,9 @@ int          c4gpu_batch_run_regions(c4gpu_batch *b, const c4gpu_region *regions
  * c4gpu_batch_swap_stage; call it again after the next swap) and to every run that follows: annotated positions carry a matrix
  * row of their own, the batch's passes take the kernels that keep every validity mask and the 32-bit arithmetic (a score of
  * -987654321 is outside every packed-pass guard), one launch lane.  Models without a 1:1 DNA match calc are not affected (the
- * reference's other match functions have their own, coding-model rules: match.c:490-546, not on the accelerated path). */
+ * reference's other match functions have their own, coding-model rules: match.c:490-546, not on the accelerated path).
+ * A batch whose model has a codon match calc (C4GPU_CALC_MATCH_CODON: "ungapped:trans", "coding2coding") refuses annotations
+ * with an error (-1, c4gpu_last_error): the reference's 3:3 match vetoes by frame (match.c:513-519), which is not built. */
 int         c4gpu_batch_set_annotation(c4gpu_batch *b, const int32_t *cds_start, const int32_t *cds_length);
 
 /* Per-pair score thresholds for the full runs (what = 2) and c4gpu_batch_next_paths: what

@@ -69,6 +69,12 @@ int  c4m_transition_id(const c4m_model *m, int transition);          /* id after
 int  c4m_flatten(const c4m_model *m, c4gpu_model *out);
 
 /* the reference's model constructors, on top of the builder (for callers that want the c4m object) */
+/* Besides C4GPU_ALPHABET_DNA / _PROTEIN, c4m_ungapped_create and c4m_affine_create take C4M_ALPHABET_CODON for BOTH alphabets:
+ * two DNA sequences, both translated (Match_Type_CODON2CODON, match advance 3/3; the closed model's alphabets are DNA / DNA).
+ * c4m_ungapped_create then builds "ungapped:codon"; c4m_affine_create builds "affine:local:codon", the base of
+ * c4m_coding2coding_create, for C4M_AFFINE_LOCAL only and returns NULL for the other scopes (the reference has no such model,
+ * coding2coding.c:54, and there are no kernels for one).  c4gpu_model_get never takes it from a caller. */
+#define C4M_ALPHABET_CODON 2
 c4m_model *c4m_ungapped_create(int query_alphabet, int target_alphabet, const c4gpu_params *p);  /* ungapped.c:122 */
 c4m_model *c4m_affine_create(int scope_type, int query_alphabet, int target_alphabet,
                              const c4gpu_params *p);                                           /* affine.c:150  */
@@ -79,6 +85,7 @@ c4m_model *c4m_est2genome_create(const c4gpu_params *p);                        
 c4m_model *c4m_protein2dna_create(int scope_type, const c4gpu_params *p);                       /* protein2dna.c:56 */
 c4m_model *c4m_phase_create(const c4gpu_params *p);                                             /* phase.c:354 (protein query, target introns) */
 c4m_model *c4m_protein2genome_create(int scope_type, const c4gpu_params *p);                    /* protein2genome.c:44 */
+c4m_model *c4m_coding2coding_create(const c4gpu_params *p);                                     /* coding2coding.c:50 */
 
 /* Affine_Model_Type, src/model/affine.h */
 enum { C4M_AFFINE_GLOBAL = 0, C4M_AFFINE_BESTFIT, C4M_AFFINE_LOCAL, C4M_AFFINE_OVERLAP };

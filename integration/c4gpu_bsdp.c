@@ -842,6 +842,7 @@ GAM_Result *GAM_Result_heuristic_create(GAM *gam, Comparison *comparison){
     register gboolean batchable = (shim_batch_size() > 0) && (!gam->gas->use_gapped_extension) && gam->heuristic
         && (bsdp_mode == BSDP_OFF)
         && (!shim_model_has_query_span(gam->heuristic->model))   /* no compiled families for a span on both axes (ner) */
+        && (!shim_model_has_wide_query_advance(gam->heuristic->model))   /* nor derived families with a query advance of 3 */
         && (!Comparison_Param_get_HSPSet_Argument_Set(comparison->param)->geneseed_threshold)
         && (shim_env("C4GPU_BSDP_HOST") || (shim_ctx_nowait() != NULL))
         && (!shim_env("C4GPU_BSDP_OFF"));

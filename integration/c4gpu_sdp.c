@@ -73,6 +73,8 @@ static gboolean sdp_eligible(GAM *gam, Comparison *comparison){
         return FALSE;
     if(shim_model_has_query_span(gam->sdp->model))         /* the device SDP has no spans along the query (ner) */
         return FALSE;
+    if(shim_model_has_wide_query_advance(gam->sdp->model)) /* ... and exchanges one query row per step (c4_sdp_wave.h) */
+        return FALSE;
     if(gam->gas->refinement != GAM_Refinement_NONE)
         return FALSE;
     if(Comparison_Param_get_HSPSet_Argument_Set(comparison->param)->geneseed_threshold)

@@ -411,7 +411,8 @@ void Seeder_add_target(Seeder *seeder, Sequence *target){
     if(off < 0)
         off = (shim_env("C4GPU_SEED_OFF") || (shim_batch_size() <= 0)) ? 1 : 0;
     shim_mark("Seeder_add_target");
-    if((!off) && (shim_env("C4GPU_SEED_HOST") || shim_ctx_nowait())){
+    /* a translated query (codon2codon: match advance 3 on the query) has a word list per query frame: the reference's walk */
+    if((!off) && (match->query->advance == 1) && (shim_env("C4GPU_SEED_HOST") || shim_ctx_nowait())){
         st = seed_state(seeder);
         if(st->hopeless)
             st = NULL;

@@ -316,6 +316,20 @@ gboolean shim_flatten_any(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out, gboo
         o->protect = c->protect;
         /* calc functions are file-static in the reference: recognised by the names the model builders give */
         if(!strcmp(c->name, "match")){
+            /* both DNA sequences translated (Match_Type_CODON2CODON: ungapped:trans, coding2coding): the match transition
+             * advances 3/3.  Its annotation veto depends on the frame (match.c:513-519): such pairs stay with the reference */
+            register gboolean codon = FALSE;
+            for(j = 0; j < m->transition_list->len; j++){
+                C4_Transition *t = m->transition_list->pdata[j];
+                if((t->calc == c) && (t->advance_query == 3) && (t->advance_target == 3))
+                    codon = TRUE;
+                }
+            if(codon){
+                if(out->query_alphabet || out->target_alphabet || ud->query->annotation || ud->target->annotation)
+                    return FALSE;
+                o->kind = C4GPU_CALC_MATCH_CODON;
+                continue;
+                }
             if(out->query_alphabet && !out->target_alphabet) o->kind = C4GPU_CALC_MATCH_P2D;
             else if(out->query_alphabet && out->target_alphabet) o->kind = C4GPU_CALC_MATCH_PROTEIN;
             else if(!out->query_alphabet && !out->target_alphabet) o->kind = C4GPU_CALC_MATCH_DNA;
@@ -371,7 +385,15 @@ gboolean shim_flatten_any(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out, gboo
         for(j = 0; j < s->dst_transition_list->len; j++)
             o->dst_transition_mask |= ((uint64_t)1) << ((C4_Transition*)s->dst_transition_list->pdata[j])->id;
         }
+    /* a query advance above one: the two whole models have kernels (exhaustive seam); the models BSDP derives from them do
+     * not, and decline here instead of failing at batch creation call after call */
+    if(shim_model_has_wide_query_advance(m) && (c4gpu_model_device_family(out) < 0))
+        return FALSE;
     return c4gpu_model_is_accelerated(out);
+    }
+
+gboolean shim_model_has_wide_query_advance(C4_Model *m){
+    return m->max_query_advance > 1;
     }
 
 gboolean shim_model_has_query_span(C4_Model *m){

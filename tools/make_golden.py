@@ -230,6 +230,113 @@ def ner_pairs(rng, n, alphabet, tag, blocks=(25, 90), long_from=None):
     return cases
 
 
+def coding_pair(rng, n_aa, flank_q=0, flank_t=0, sub=0.08, codon_indels=1, shifts=(), decorate=None):
+    """A pair of homologous coding sequences for the translated models (ungapped:trans, coding2coding): a random peptide coded
+    with random synonymous codons on each side, with planted amino-acid substitutions, codon insertions / deletions and
+    frameshifts -- `shifts` lists (axis, bases): "q" / "t" and 1 or 2 bases inserted on that axis -- and flanks of flank_q /
+    flank_t random bases in front (1 or 2: the aligned region starts off frame).  decorate: "lower" (a lower-case stretch), "n"
+    (N runs), "iupac" (two-base ambiguity codes), "stop" (stop codons on both sides)."""
+    pep = [rng.choice(AA) for _ in range(n_aa)]
+    qc = [rng.choice(CODON[a]) for a in pep]
+    tc = [rng.choice(CODON[rng.choice(AA) if rng.random() < sub else a]) for a in pep]
+    for _ in range(codon_indels if n_aa >= 12 else 0):
+        at = rng.randint(4, n_aa - 4)
+        if rng.random() < 0.5:
+            tc[at:at] = [rng.choice(CODON[rng.choice(AA)]) for _ in range(rng.randint(1, 2))]
+        else:
+            qc[at:at] = [rng.choice(CODON[rng.choice(AA)]) for _ in range(rng.randint(1, 2))]
+    if decorate == "stop" and n_aa >= 8:
+        at = rng.randint(3, n_aa - 3)
+        qc[at], tc[at] = rng.choice(CODON["*"]), rng.choice(CODON["*"])
+    for axis, bases in shifts:
+        side = qc if axis == "q" else tc
+        at = rng.randint(len(side) // 4, 3 * len(side) // 4)
+        side[at] = side[at] + rand_dna(rng, bases)
+    q, t = "".join(qc), "".join(tc)
+    if decorate == "lower":
+        q = q[:len(q) // 3] + q[len(q) // 3:2 * len(q) // 3].lower() + q[2 * len(q) // 3:]
+        t = t.lower()
+    elif decorate == "n":
+        q = "".join("N" if rng.random() < 0.04 else c for c in q)
+        t = "".join("N" if rng.random() < 0.04 else c for c in t)
+    elif decorate == "iupac":
+        amb = {"A": "RMW", "C": "YMS", "G": "RKS", "T": "YKW"}
+        q = "".join(rng.choice(amb[c]) if rng.random() < 0.05 else c for c in q)
+        t = "".join(rng.choice(amb[c]) if rng.random() < 0.05 else c for c in t)
+    return rand_dna(rng, flank_q) + q + rand_dna(rng, rng.choice([0, 1, 2, 7])), rand_dna(rng, flank_t) + t + rand_dna(rng, rng.choice([0, 1, 2, 5]))
+
+
+def coding_cases(rng, tag, full=True):
+    """The case list of the translated models' sets: see coding_pair.  full: with the shapes that matter to the device kernels --
+    queries of 1 to 5 bases, of 18 and 19 bases (the edge of the memory rule, query_length <= 6 * max_query_advance), queries of
+    400 and 700 bases (the kernels give a lane four query rows: strips of 256 rows, so the three rows handed from strip to strip
+    cross one and two strip boundaries) against targets long enough for several checkpoints under -D 0."""
+    specs = [dict(n_aa=30), dict(n_aa=34, flank_q=1), dict(n_aa=34, flank_t=2), dict(n_aa=40, flank_q=2, flank_t=1),
+             dict(n_aa=44, shifts=[("q", 1)]), dict(n_aa=44, shifts=[("q", 2)], flank_q=1),
+             dict(n_aa=44, shifts=[("t", 1)], flank_t=2), dict(n_aa=44, shifts=[("t", 2)]),
+             dict(n_aa=60, shifts=[("q", 1), ("t", 2)], codon_indels=2), dict(n_aa=36, decorate="lower"),
+             dict(n_aa=36, decorate="n"), dict(n_aa=36, decorate="iupac", flank_q=2), dict(n_aa=36, decorate="stop", flank_t=1)]
+    cases = [("%s%03d" % (tag, k), ) + coding_pair(rng, **sp) for k, sp in enumerate(specs)]
+    if full:
+        k = len(cases)
+        for ql in (1, 2, 3, 4, 5, 18, 19):
+            t = coding_pair(rng, 20)[1]
+            at = rng.randint(0, len(t) - ql)
+            cases.append(("%s%03d" % (tag, k), t[at:at + ql], t))
+            k += 1
+        for n_aa, shifts in ((133, [("q", 1), ("t", 1)]), (233, [("q", 2), ("t", 2), ("q", 1)])):
+            cases.append(("%s%03d" % (tag, k), ) + coding_pair(rng, n_aa, flank_q=1, flank_t=2, shifts=shifts, codon_indels=3))
+            k += 1
+    return cases
+
+
+CODON_RYO = "ryo: %qi %ti %s %pi %ps %et %em %V\\n"
+# the reference-binary-made sets of the translated models: exonerate flags (the first is the model); --exhaustive runs align
+# both strands of both sequences (translate_both), and the recorded stdout holds every alignment of the run
+CODON_CLI_SETS = {
+    "codon_cli_coding2coding": ["--model", "coding2coding"],
+    "codon_cli_coding2coding_alt": ["--model", "coding2coding", "--codongapopen", "-11", "--codongapextend", "-3", "--frameshift", "-13",
+                                    "--proteinsubmat", "pam250"],
+    "codon_cli_ungapped_trans": ["--model", "ungapped:trans"],
+}
+
+
+def run_codon_cli(name):
+    """One JSON per set: the inputs and the stdout lines of exonerate --model <m> --exhaustive yes --subopt no -n 1 with every
+    report switched on, one run per pair (Command line / Hostname / ##date lines dropped, as in run_ner_cli)."""
+    flags = CODON_CLI_SETS[name]
+    rng = random.Random(8100 + len(name))
+    cases = coding_cases(rng, "ccli", full=False)[1:9:2] + coding_cases(rng, "cclj", full=False)[9:11]
+    # ... the last two with the target, then the query, reverse-complemented: their best alignment is on a minus strand
+    comp = str.maketrans("ACGTNacgtn", "TGCANtgcan")
+    cases[4] = (cases[4][0], cases[4][1], cases[4][2].translate(comp)[::-1])
+    cases[5] = (cases[5][0], cases[5][1].translate(comp)[::-1], cases[5][2])
+    out = {"flags": flags[2:], "model": flags[1], "ryo": CODON_RYO, "pairs": []}
+    for cid, q, t in cases:
+        with tempfile.TemporaryDirectory() as d:
+            qf, tf = os.path.join(d, "q.fa"), os.path.join(d, "t.fa")
+            with open(qf, "w") as f:
+                f.write(">%s query of %s\n%s\n" % (cid, name, q))
+            with open(tf, "w") as f:
+                f.write(">tg_%s\n%s\n" % (cid, t))
+            cmd = [REF_EXONERATE] + flags + ["--exhaustive", "yes", "--subopt", "no", "-n", "1",
+                   "--showalignment", "yes", "--showsugar", "yes", "--showcigar", "yes", "--showvulgar", "yes",
+                   "--showtargetgff", "yes", "--showquerygff", "yes", "--ryo", CODON_RYO, qf, tf]
+            r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, check=True)
+        lines = [l for l in r.stdout.decode().split("\n")
+                 if not l.startswith(("Command line:", "Hostname:", "##date "))]
+        sugar = [l for l in lines if l.startswith("sugar:")][0].split()
+        qs, ts = sugar[4], sugar[8]
+        # the same alignment as transition ids: refdump on the strands the binary chose (its first path is the binary's -n 1)
+        rec = run(flags[1], [(cid, q.translate(comp)[::-1] if qs == "-" else q, t.translate(comp)[::-1] if ts == "-" else t)], 32, flags[2:])[0]
+        assert rec["vulgar"].split()[10:] == [l for l in lines if l.startswith("vulgar:")][0].split()[10:] and rec["path_score"] == int(sugar[9]), (name, cid)
+        out["pairs"].append({"id": cid, "qdef": "query of %s" % name, "tid": "tg_%s" % cid, "query": q, "target": t, "stdout": lines,
+                             "qstrand": qs, "tstrand": ts, "score": rec["path_score"], "region": rec["region"], "ops": rec["ops"]})
+    with open(os.path.join(OUT, name + ".json"), "w") as f:
+        json.dump(out, f, separators=(",", ":"))
+    print(name, len(out["pairs"]), "pairs,", sum(len(p["stdout"]) for p in out["pairs"]), "lines")
+
+
 REF_EXONERATE = os.path.join(ROOT, "oracle", "_ref", "exonerate")
 NER_CLI_RYO = "ryo: %s %pi %et %em %V\\n"
 # the parameter points of the reference-binary-made ner sets: (alphabet, exonerate flags); the tests turn the flags into a
@@ -738,11 +845,38 @@ def main():
     for name in sorted(NER_CLI_SETS):
         if (not only) or name in only:
             run_ner_cli(name)
+    # the translated models (ungapped.c:106-166 with CODON2CODON, coding2coding.c:50-66): match advance 3/3.  refdump takes any
+    # Model_Type name; the reference itself is the yardstick (the CPU oracle has no codon match)
+    cr = random.Random(3303)
+    c2c = coding_cases(cr, "c2c")
+    ugt = coding_cases(cr, "ugt")
+    # ... for the sub-optimal loop: a second, more diverged copy of the query's middle further along the target
+    c2c_sub = [(cid, q, t + rand_dna(cr, 11 + k) + substitute(cr, q[len(q) // 4:3 * len(q) // 4], 0.06, "ACGT") + rand_dna(cr, k))
+               for k, (cid, q, t) in enumerate(coding_cases(cr, "c2s", full=False)[:6])]
+    cso = ("--suboptmax", "4", "--suboptthreshold", "30")
+    calt = ("--codongapopen", "-11", "--codongapextend", "-3", "--frameshift", "-13", "--proteinsubmat", "pam250")
+    d0 = lambda cases: [c for c in cases if len(c[1]) >= 19 and len(c[2]) >= 19]
+    sets.append(("coding2coding", "coding2coding", c2c, 32, ()))
+    sets.append(("coding2coding_D0", "coding2coding", d0(c2c), 0, ()))
+    sets.append(("coding2coding_subopt", "coding2coding", c2c_sub, 32, cso))
+    sets.append(("coding2coding_subopt_D0", "coding2coding", c2c_sub[:3], 0, cso))
+    sets.append(("coding2coding_codonalt", "coding2coding", c2c[:13], 32, calt))
+    sets.append(("coding2coding_codonalt_D0", "coding2coding", c2c[4:13] + c2c[-2:], 0, calt))
+    sets.append(("ungapped_trans", "ungapped:trans", ugt, 32, ()))
+    sets.append(("ungapped_trans_D0", "ungapped:trans", d0(ugt), 0, ()))
+    sets.append(("ungapped_trans_subopt", "ungapped:trans", c2c_sub, 32, cso))
+    sets.append(("ungapped_trans_codonalt", "ungapped:trans", ugt[:13], 32, calt))
+    for name in sorted(CODON_CLI_SETS):
+        if (not only) or name in only:
+            run_codon_cli(name)
     for name, model, cases, dpm, extra in sets:
         if only and name not in only:
             continue
         recs = run(model, cases, dpm, extra)
-        if name.endswith("_subopt_D0") or name.startswith("ner_"):      # the point sets are those of the -D 32 twin (ner: none): keep the files small
+        if name.startswith(("coding2coding", "ungapped_trans")):
+            # every record of these sets carries a path: the tests compare ops on all of them
+            assert all(r.get("ops") for r in recs), (name, [r["id"] for r in recs if not r.get("ops")])
+        if name.endswith("_subopt_D0") or name.startswith(("ner_", "coding2coding", "ungapped_trans")):      # the point sets are those of the -D 32 twin (ner: none): keep the files small
             for r in recs:
                 for a in r.get("subopt", []):
                     a.pop("points", None)
