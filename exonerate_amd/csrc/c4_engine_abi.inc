@@ -403,6 +403,9 @@ int c4gpu_batch_viterbi_model(c4gpu_batch *b, const c4gpu_model *model, int mode
         if (it == b->extra.end()) {
             std::unique_ptr<c4gpu_batch::ExtraEngine> e(new c4gpu_batch::ExtraEngine);
             e->model = *model;
+            // an annotated batch's codes carry row 24: the other model's engine arms the same veto row and guards
+            // (c4gpu_batch_set_annotation drops these engines whenever that changes)
+            e->eng.annotated = b->eng.annotated;
             if (e->eng.init(b->ctx, &e->model, &b->params)) return -1;
             // the resident arrays were prepared for the batch's own model: the other model must read the same ones
             if (family_is_p2d(e->eng.family) != family_is_p2d(b->eng.family) || family_is_codon(e->eng.family) != family_is_codon(b->eng.family) ||
@@ -680,6 +683,31 @@ int c4gpu_batch_set_annotation(c4gpu_batch *b, const int32_t *cds_start, const i
                                "] matches translated codons; the frame-dependent annotation veto of the 3:3 match is not supported");
                 return -1;
             }
+        // the veto belongs to the 1:1 DNA match calc alone (Engine::init_host decides it the same way): a model without one
+        // keeps its codes, its parameter block, its kernels and its second lane
+        bool dna_match = false, protein = false;
+        for (int c = 0; c < b->model.n_calcs; c++) {
+            const int kind = b->model.calcs[c].kind;
+            dna_match |= kind == C4GPU_CALC_MATCH_DNA;
+            protein |= kind == C4GPU_CALC_MATCH_PROTEIN || kind == C4GPU_CALC_MATCH_P2D || kind == C4GPU_CALC_MATCH_CODON;
+        }
+        if (!dna_match || protein) return 0;
+        // pairs that were handed the same query buffer read the same codes (ResidentSeqs::build: one qoff): one annotation
+        // between them, "none" being a value too; refused before anything is touched.  An empty query holds no codes and does
+        // not advance the offsets (its qoff is the next query's): it shares nothing and its annotation reaches nothing
+        {
+            std::map<long long, int> first;
+            for (int i = 0; i < n; i++) {
+                if (b->seqs.qlen[i] == 0) continue;
+                auto it = first.emplace(b->seqs.qoff[i], i).first;
+                const int j = it->second;
+                if (cds[3 * i] != cds[3 * j] || cds[3 * i + 1] != cds[3 * j + 1]) {
+                    c4h::set_error("c4gpu_batch_set_annotation: pairs " + std::to_string(j) + " and " + std::to_string(i) +
+                                   " share a query buffer and carry different annotations (give each its own copy of the query)");
+                    return -1;
+                }
+            }
+        }
         if (any != b->eng.annotated) {
             // the engine's guards and its parameter block follow (Engine::init_host): the veto row armed, the kernels that keep
             // every validity mask, no packed pass, one launch lane (the second lane's engine is built from the same

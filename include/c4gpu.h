@@ -379,8 +379,12 @@ int          c4gpu_batch_run_regions(c4gpu_batch *b, const c4gpu_region *regions
  * both NULL: no pair has one).  Applies to the sequences the batch holds NOW (after c4gpu_batch_create or
  * c4gpu_batch_swap_stage; call it again after the next swap) and to every run that follows: annotated positions carry a matrix
  * row of their own, the batch's passes take the kernels that keep every validity mask and the 32-bit arithmetic (a score of
- * -987654321 is outside every packed-pass guard), one launch lane.  Models without a 1:1 DNA match calc are not affected (the
- * reference's other match functions have their own, coding-model rules: match.c:490-546, not on the accelerated path).
+ * -987654321 is outside every packed-pass guard), one launch lane; the models of c4gpu_batch_viterbi_model follow the batch.
+ * Pairs that were given the same query buffer (same pointer and length) share one copy of the query on the device and must
+ * carry the same annotation, "none" included: a call that gives them different ones is refused (-1, c4gpu_last_error) and
+ * changes nothing -- hand each such pair a copy of the query of its own.  Models without a 1:1 DNA match calc are not affected
+ * (the call returns 0 and changes nothing: same codes, same kernels; the reference's other match functions have their own,
+ * coding-model rules: match.c:490-546, not on the accelerated path).
  * A batch whose model has a codon match calc (C4GPU_CALC_MATCH_CODON: "ungapped:trans", "coding2coding") refuses annotations
  * with an error (-1, c4gpu_last_error): the reference's 3:3 match vetoes by frame (match.c:513-519), which is not built. */
 int         c4gpu_batch_set_annotation(c4gpu_batch *b, const int32_t *cds_start, const int32_t *cds_length);

@@ -43,7 +43,12 @@ for _tag, _bases in (("hugegap", ("affine_local_dna", "est2genome", "protein2dna
 # --annotation (match.c:276-281): DNA queries with a CDS annotation, rec["cds"] = [cds_start, cds_length]; made by the reference
 # with the annotation attached to the query Sequence (oracle/refdump.c, tools/make_golden.py: annotated)
 ANNOT_SETS = {"est2genome_annot": ("est2genome", 0, 0), "est2genome_annot_D0": ("est2genome", 0, 0),
-              "affine_local_dna_annot": ("affine:local", 0, 0), "affine_local_dna_annot_D0": ("affine:local", 0, 0)}
+              "affine_local_dna_annot": ("affine:local", 0, 0), "affine_local_dna_annot_D0": ("affine:local", 0, 0),
+              # the other scopes and the model without gap states: the veto sits in the match calc they share
+              "affine_global_dna_annot": ("affine:global", 0, 0), "affine_bestfit_dna_annot": ("affine:bestfit", 0, 0),
+              "affine_overlap_dna_annot": ("affine:overlap", 0, 0), "ungapped_dna_annot": ("ungapped", 0, 0)}
+# ... and through the GAM sub-optimal loop (rec["cds"], rec["subopt"], rec["threshold"]; --suboptmax 4)
+ANNOT_SUBOPT_SETS = {"est2genome_annot_subopt": ("est2genome", 0, 0)}
 
 
 # sets with the GAM sub-optimal loop (rec["subopt"] = successive alignments, rec["threshold"])
@@ -66,6 +71,14 @@ for _tag, _mt, _qa, _ta, _ms in (("affine_local", "affine:local", 0, 0, (2,)), (
         DERIVED_SETS["derived_%s%s_start" % (_tag, _sfx)] = (_mt, _qa, _ta, (0, _m, 0, 4))
         DERIVED_SETS["derived_%s%s_end" % (_tag, _sfx)] = (_mt, _qa, _ta, (_m, 1, 4, 0))
         DERIVED_SETS["derived_%s%s_join" % (_tag, _sfx)] = (_mt, _qa, _ta, (_m, _m, 4, 4))
+
+
+def set_spec(name):
+    """(model type, query alphabet, target alphabet) of a set that is no derived-model set."""
+    for sets in (SETS, ANNOT_SETS, SUBOPT_SETS, ANNOT_SUBOPT_SETS):
+        if name in sets:
+            return sets[name]
+    raise KeyError(name)
 
 
 def load_set(name):
@@ -132,7 +145,7 @@ def get_model(lib, params, name):
         m = _abi.Model()
         assert lib.c4gpu_model_get_derived(mt.encode(), qa, ta, params, src, dst, ss, es, m, None) == 0
         return m
-    mt, qa, ta = SETS[name] if name in SETS else ANNOT_SETS[name] if name in ANNOT_SETS else SUBOPT_SETS[name]
+    mt, qa, ta = set_spec(name)
     m = _abi.Model()
     assert lib.c4gpu_model_get(mt.encode(), qa, ta, params, m) == 0
     return m

@@ -18,13 +18,15 @@ from golden_util import GOLDEN_DIR, apply_flags, load_set
 REFDUMP_SETS = {"ner_dna_open0": (0, 0), "ner_protein_open0": (1, 1), "ner_dna_open0_D0": (0, 0)}
 # ... with the GAM sub-optimal loop (rec["subopt"], rec["threshold"]; --suboptmax 4: at most SUBOPT_MAX alignments per pair)
 SUBOPT_SETS = {"ner_dna_open0_subopt": (0, 0), "ner_dna_open0_subopt_D0": (0, 0)}
+# ... with a CDS annotation on the query (rec["cds"], exonerate's --annotation: no 1:1 DNA match inside it)
+ANNOT_SETS = {"ner_dna_open0_annot": (0, 0), "ner_dna_open0_annot_D0": (0, 0)}
 CLI_SETS = ["ner_cli_default", "ner_cli_open35", "ner_cli_protein", "ner_cli_hugegap", "ner_cli_hugeopen"]
 NER_OPEN_DEFAULT = -20           # ner.c:31-33
 SUBOPT_MAX = 4
 
 
 def open0_model(name):
-    qa, ta = REFDUMP_SETS[name] if name in REFDUMP_SETS else SUBOPT_SETS[name]
+    qa, ta = REFDUMP_SETS[name] if name in REFDUMP_SETS else ANNOT_SETS[name] if name in ANNOT_SETS else SUBOPT_SETS[name]
     return ex.Model("ner", query_alphabet=qa, target_alphabet=ta, ner_open=0)
 
 
@@ -83,5 +85,5 @@ def ner_block_crosses_a_line_break(lines):
     return False
 
 
-__all__ = ["REFDUMP_SETS", "SUBOPT_SETS", "CLI_SETS", "NER_OPEN_DEFAULT", "SUBOPT_MAX", "open0_model", "load_cli", "cli_lines",
+__all__ = ["REFDUMP_SETS", "SUBOPT_SETS", "ANNOT_SETS", "CLI_SETS", "NER_OPEN_DEFAULT", "SUBOPT_MAX", "open0_model", "load_cli", "cli_lines",
            "oracle_alignment", "vulgar_labels", "ner_block_crosses_a_line_break", "load_set", "_abi"]

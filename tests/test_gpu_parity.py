@@ -10,7 +10,7 @@ import pytest
 import exonerate_amd as ex
 from exonerate_amd import _abi
 import oracle_lib
-from golden_util import SETS, SUBOPT_SETS, DERIVED_SETS, SPAN_SETS, ANNOT_SETS, load_set, expected, set_params
+from golden_util import SETS, SUBOPT_SETS, DERIVED_SETS, SPAN_SETS, ANNOT_SETS, load_set, expected, set_params, set_spec
 
 pytestmark = pytest.mark.gpu
 
@@ -26,7 +26,7 @@ def _model(name):
     if name in DERIVED_SETS:
         mt, qa, ta, (src, dst, ss, es) = DERIVED_SETS[name]
         return ex.Model.derived(mt, src, dst, ss, es, qa, ta)
-    mt, qa, ta = SETS[name] if name in SETS else ANNOT_SETS[name] if name in ANNOT_SETS else SUBOPT_SETS[name]
+    mt, qa, ta = set_spec(name)
     return ex.Model(mt, qa, ta, params=set_params(_abi.load(), name))
 
 

@@ -11,7 +11,7 @@ import exonerate_amd as ex
 from exonerate_amd import _abi
 import oracle_lib
 from golden_util import expected
-from ner_cases import REFDUMP_SETS, SUBOPT_SETS, NER_OPEN_DEFAULT, SUBOPT_MAX, open0_model, load_set
+from ner_cases import REFDUMP_SETS, SUBOPT_SETS, ANNOT_SETS, NER_OPEN_DEFAULT, SUBOPT_MAX, open0_model, load_set
 
 
 @pytest.mark.parametrize("qa,ta,match", [(0, 0, "dna2dna"), (1, 1, "protein2protein")])
@@ -99,6 +99,30 @@ def test_oracle_on_the_ner_table_matches_reference_vectors(name):
         names = {model.c.transitions[o[0]].name.decode() for rec in recs for o in rec["ops"]}
         assert {"match to ner", "ner loop insert", "ner loop delete", "ner to match"} <= names
         assert sum(300 <= rec["qlen"] <= 1200 for rec in recs) >= 3 and max(rec["qlen"] for rec in recs) > 512
+
+
+@pytest.mark.parametrize("name", sorted(ANNOT_SETS))
+def test_oracle_on_the_ner_table_matches_reference_vectors_with_annotation(name):
+    """--annotation (match.c:276-281): the ner model's DNA form scores its matches with the same 1:1 DNA match function, so a
+    query position inside the annotated CDS (rec["cds"]) can only sit in a gap or in a non-equivalenced region."""
+    model = open0_model(name)
+    recs = load_set(name)
+    assert recs
+    changed = 0
+    try:
+        for rec in recs:
+            q, t = rec["query"].encode(), rec["target"].encode()
+            assert rec["model"] == model.name
+            oracle_lib.set_annotation(None)
+            plain = oracle_lib.find_path(model.c, model.params, q, t, dpmemory=rec["dpmemory"], qid=rec["id"])
+            oracle_lib.set_annotation(rec["cds"])
+            assert oracle_lib.find_score(model.c, model.params, q, t) == rec["score"], rec["id"]
+            got = oracle_lib.find_path(model.c, model.params, q, t, dpmemory=rec["dpmemory"], qid=rec["id"])
+            assert got == (expected(rec) if "path_score" in rec else None), rec["id"]
+            changed += got != plain
+    finally:
+        oracle_lib.set_annotation(None)
+    assert 3 * changed >= len(recs)           # the annotation is what decides these records
 
 
 @pytest.mark.parametrize("name", sorted(SUBOPT_SETS))

@@ -842,6 +842,17 @@ def main():
     sets.append(("ner_dna_open0_D0", "ner", [c for c in ner_dna if len(c[1]) >= 13 and len(c[2]) >= 13][::2], 0, ()))
     sets.append(("ner_dna_open0_subopt", "ner", ner_sub, 32, nso))
     sets.append(("ner_dna_open0_subopt_D0", "ner", ner_sub[:2], 0, nso))
+    # --annotation on the other models with a 1:1 DNA match (the veto sits in the match calc, whatever the scope, the states
+    # around it or the memory route), and through the sub-optimal loop (the veto and the SubOpt blocking meet in one cell)
+    da = [c for c in d if len(c[1]) >= 13 and len(c[2]) >= 13]
+    sets.append(("affine_global_dna_annot", "affine:global", annotated(da[:12], 45), 32, ()))
+    sets.append(("affine_bestfit_dna_annot", "affine:bestfit", annotated(da[:12], 46), 32, ()))
+    sets.append(("affine_overlap_dna_annot", "affine:overlap", annotated(da[:12], 47), 32, ()))
+    sets.append(("ungapped_dna_annot", "ungapped", annotated(da[:12], 48), 32, ()))
+    ner_annot = annotated(ner_pairs(random.Random(7312), 10, "ACGT", "nera", blocks=(25, 50)), 49)
+    sets.append(("ner_dna_open0_annot", "ner", ner_annot, 32, ()))
+    sets.append(("ner_dna_open0_annot_D0", "ner", ner_annot[:8], 0, ()))
+    sets.append(("est2genome_annot_subopt", "est2genome", annotated([c for c in sub_est if len(c[1]) <= 200][:6], 50), 32, nso))
     for name in sorted(NER_CLI_SETS):
         if (not only) or name in only:
             run_ner_cli(name)
@@ -876,7 +887,18 @@ def main():
         if name.startswith(("coding2coding", "ungapped_trans")):
             # every record of these sets carries a path: the tests compare ops on all of them
             assert all(r.get("ops") for r in recs), (name, [r["id"] for r in recs if not r.get("ops")])
-        if name.endswith("_subopt_D0") or name.startswith(("ner_", "coding2coding", "ungapped_trans")):      # the point sets are those of the -D 32 twin (ner: none): keep the files small
+        if any(len(c) > 3 for c in cases):
+            # an annotated set is worth its place only where the annotation decides: the reference's result for the same pairs
+            # without it (score, path, successive paths) must differ in at least a third of the records
+            # (the two sets from before that rule hold 14; every later one at most 12)
+            assert len(recs) <= (14 if name in ("est2genome_annot", "affine_local_dna_annot") else 12), name
+            what = lambda r: (r["score"], r.get("path_score"), r.get("region"), r.get("ops"),
+                              [(a["path_score"], a["region"], a["ops"]) for a in r.get("subopt", [])])
+            plain = run(model, [c[:3] for c in cases], dpm, extra)
+            differ = sum(what(a) != what(b) for a, b in zip(recs, plain))
+            assert 3 * differ >= len(recs), (name, differ, len(recs))
+            print(name, "annotation decides", differ, "of", len(recs))
+        if name.endswith("_subopt_D0") or name.endswith("_annot_subopt") or name.startswith(("ner_", "coding2coding", "ungapped_trans")):      # the point sets are those of the -D 32 twin (ner: none): keep the files small
             for r in recs:
                 for a in r.get("subopt", []):
                     a.pop("points", None)
