@@ -330,6 +330,20 @@ static c4gpu_score calc_score(odata *od, int calc, int32_t qpos, int32_t tpos){
                               | (p->nt2d[od->target[tp3]] << 8)]];
             return p->protein_submat[p->submat_index[od->query[qpos]]][p->submat_index[aa]];
             }
+        case C4GPU_CALC_MATCH_CODON: {   /* Match_3_3_split_score_func match.c:508-530 + Translate_base translate.h:73: inside
+                                          * an annotation only codons of the CDS, in its frame, match */
+            uint8_t qaa, taa;
+            if((oracle_cds_length > 0) && ((qpos < oracle_cds_start) || (qpos >= oracle_cds_start + oracle_cds_length)
+                                        || ((qpos % 3) != (oracle_cds_start % 3))))
+                return LOW;
+            qaa = p->aa[p->trans[ p->nt2d[od->query[qpos]]
+                               | (p->nt2d[od->query[qpos+1]] << 4)
+                               | (p->nt2d[od->query[qpos+2]] << 8)]];
+            taa = p->aa[p->trans[ p->nt2d[od->target[tpos]]
+                               | (p->nt2d[od->target[tpos+1]] << 4)
+                               | (p->nt2d[od->target[tpos+2]] << 8)]];
+            return p->protein_submat[p->submat_index[qaa]][p->submat_index[taa]];
+            }
         default:
             fprintf(stderr, "oracle: calc kind %d not restated\n", c->kind);
             abort();

@@ -857,7 +857,7 @@ def main():
         if (not only) or name in only:
             run_ner_cli(name)
     # the translated models (ungapped.c:106-166 with CODON2CODON, coding2coding.c:50-66): match advance 3/3.  refdump takes any
-    # Model_Type name; the reference itself is the yardstick (the CPU oracle has no codon match)
+    # Model_Type name; these records pin the CPU oracle's 3:3 match as well (tests/test_oracle_codon.py)
     cr = random.Random(3303)
     c2c = coding_cases(cr, "c2c")
     ugt = coding_cases(cr, "ugt")
