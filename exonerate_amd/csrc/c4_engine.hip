@@ -25,6 +25,7 @@
 #include "c4_config.h"
 #include "c4_memrule.h"
 #include "c4_launch.h"
+#include "c4_kernel_choice.h"
 #include "c4_sdp_launch.h"
 #include "c4_sdp_host.h"
 

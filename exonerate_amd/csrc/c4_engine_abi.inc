@@ -548,8 +548,7 @@ int c4gpu_stage_load(c4gpu_stage *st, const c4gpu_pair *pairs, int32_t n_pairs) 
         // the packed passes' splice array: written by the splice kernel itself here (ss16_kernel's formula with the calc
         // constants of the pre-splice transitions as `fold`), where the first packed launch would otherwise build it inside
         // the step (C4GPU_PK16=0: no packed pass, no array)
-        const bool pk = !(c4cfg::is(c4cfg::PK16, 0)) && n_pairs >= 2 && st->eng.pk16_params_ok &&
-                        st->eng.family == FAM_EST2GENOME;
+        const bool pk = pk16_enabled(st->eng.family, st->eng.pk16_params_ok, n_pairs, Switches::from_config());
         SpliceFold fold{{0, 0, 0, 0}};
         for (int i = 0; i < st->model.n_calcs; i++)
             if (st->model.calcs[i].kind == C4GPU_CALC_SPLICE_PRE) fold.add[st->model.calcs[i].param & 3] = st->model.calcs[i].value;

@@ -56,8 +56,7 @@ int find_path_batch(Engine &eng, const ResidentSeqs &seqs, int dpmemory_mb, c4gp
         // windows save 9 (step on two lanes 442 -> 436 ms; 2 048: 438; profiles/r04_kshift_sweep.log)
         // (4 096 only where the packed pass will really run: a call with a pair that does not fit its 16 bits -- a long query, a
         // small --intronpenalty -- or with C4GPU_PK16=0 dumps 32-bit rows, for which 8 192 is the better interval)
-        bool pk16_serves = eng.family == FAM_EST2GENOME && eng.pk16_params_ok && region_pairs.size() >= 2 &&
-                           !(c4cfg::is(c4cfg::PK16, 0)) && get_kernel_pk16(eng.family, 1) != nullptr;
+        bool pk16_serves = pk16_enabled(eng.family, eng.pk16_params_ok, (long long)region_pairs.size(), Switches::from_config());
         for (size_t x = 0; x < region_pairs.size() && pk16_serves; x++)
             pk16_serves = eng.pk16_fits(plan[region_pairs[x]].ar.query_length, plan[region_pairs[x]].ar.target_length);
         int kshift_env = pk16_serves ? 12 : 13;

@@ -53,14 +53,16 @@ struct SeedPlan {
     int hops = 0;
 };
 
-// cooperating waves per job of the region windows (SEED 2): two where the family has that form -- a job's later windows are
-// a few hundred rows high and leave fewer waves idle than with four (north-star batch: 846 against 867 ms per step) --
-// three waves: 894-916 ms, one wave with every strip boundary through HBM: 854-872 ms, four rows per lane on two waves:
-// 851-857 ms -- C4GPU_WIN_NW=4 keeps four
-int window_waves(int family) {
-    int nw = c4cfg::num(c4cfg::WIN_NW, 2);
-    if (nw != 2) nw = 4;
-    return get_kernel_mw(family, MODE_REGION, true, true, nw, false, 2) ? nw : 4;
+// a splice model's PSSM with every row at its best column: the sum of the rows' largest entries (magnitudes with `absolute`);
+// a row without a positive entry adds nothing
+double splice_best_sum(const c4gpu_splice_model &sp, bool absolute) {
+    double sum = 0;
+    for (int r = 0; r < sp.model_length && r < C4GPU_SPLICE_MAX_LEN; r++) {
+        double mx = 0;
+        for (int c = 0; c < 5; c++) mx = std::max(mx, absolute ? std::fabs((double)sp.data[r][c]) : (double)sp.data[r][c]);
+        sum += mx;
+    }
+    return sum;
 }
 
 struct Engine {
@@ -109,6 +111,7 @@ struct Engine {
     // are page-faulted in on every call)
     std::vector<int> h_order;
     std::vector<long long> h_key;
+    std::vector<int> h_qlen;                // the jobs' query lengths, as the kernel choice reads them
     std::vector<DevJob> h_jobs;
     std::vector<DevResult> h_res;
     std::vector<uint32_t> h_runs;
@@ -166,16 +169,7 @@ struct Engine {
             for (int i = 0; i < 24 * 24; i++) pmax = std::max(pmax, std::fabs((double)kp.submat[i]));
             double smax = 0;
             if (family_has_splice(family))
-                for (int k = 0; k < 4; k++) {
-                    const c4gpu_splice_model &sp = params->splice[k];
-                    double sum = 0;
-                    for (int r = 0; r < sp.model_length && r < C4GPU_SPLICE_MAX_LEN; r++) {
-                        double mx = 0;
-                        for (int c = 0; c < 5; c++) mx = std::max(mx, std::fabs((double)sp.data[r][c]));
-                        sum += mx;
-                    }
-                    smax = std::max(smax, sum + 1.0);
-                }
+                for (int k = 0; k < 4; k++) smax = std::max(smax, splice_best_sum(params->splice[k], true) + 1.0);
             // a real candidate is at least -(states x largest calc); a phantom one at most LOW + 3 calcs
             local_exact = (pmax + smax) * (m->n_states + 4) < 4.0e8;
             calc_bound = pmax + smax;
@@ -195,17 +189,8 @@ struct Engine {
             }
             if (family_has_splice(family)) {
                 // largest value a site of each kind can score: every PSSM row at its best, rounded as the predictor rounds
-                int best[4] = {0, 0, 0, 0};
-                for (int k = 0; k < 4; k++) {
-                    const c4gpu_splice_model &sp = params->splice[k];
-                    double sum = 0;
-                    for (int r = 0; r < sp.model_length && r < C4GPU_SPLICE_MAX_LEN; r++) {
-                        double mx = 0;
-                        for (int c = 0; c < 5; c++) mx = std::max(mx, (double)sp.data[r][c]);
-                        sum += mx;
-                    }
-                    best[k] = (int)std::floor(sum + 0.5) + 1;
-                }
+                int best[4];
+                for (int k = 0; k < 4; k++) best[k] = (int)std::floor(splice_best_sum(params->splice[k], false) + 0.5) + 1;
                 // an intron enters its state through a pre-splice transition and leaves it through a post-splice transition OF THE
                 // SAME STATE (est2genome: the forward strand's intron state and the reverse strand's are two states that share
                 // nothing): the most one intron can add is the best such pairing per state, not the best pre-site of one strand
@@ -244,16 +229,7 @@ struct Engine {
                 }
                 if (loop_on && family == FAM_EST2GENOME && others_cost && m->n_states <= 16) {
                     int tight[4];
-                    for (int k = 0; k < 4; k++) {
-                        const c4gpu_splice_model &sp = params->splice[k];
-                        double sum = 0;
-                        for (int r = 0; r < sp.model_length && r < C4GPU_SPLICE_MAX_LEN; r++) {
-                            double mx = 0;
-                            for (int c = 0; c < 5; c++) mx = std::max(mx, (double)sp.data[r][c]);
-                            sum += mx;
-                        }
-                        tight[k] = (int)std::floor(sum + 0.5 + 1e-3);
-                    }
+                    for (int k = 0; k < 4; k++) tight[k] = (int)std::floor(splice_best_sum(params->splice[k], false) + 0.5 + 1e-3);
                     for (int st = 0; st < m->n_states; st++) {
                         long long pre = -0x40000000LL, post = -0x40000000LL;
                         int loop = -1;
@@ -362,43 +338,48 @@ struct Engine {
         return 0;
     }
 
+    // the trace of one run_impl: a line per stage, the total when it ends
+    struct RunTrace {
+        bool on; std::chrono::steady_clock::time_point t0; int mode, n;
+        double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+        void lap(const char *what) const { if (on) fprintf(stderr, "c4gpu trace:   %-18s at %.3f ms\n", what, ms()); }
+        ~RunTrace() { if (on) fprintf(stderr, "c4gpu trace: run mode %d jobs %d host+device %.3f ms\n", mode, n, ms()); }
+    };
+    // what plan_jobs lays out for a launch (beside h_order and h_jobs): totals of the per-job buffers, the largest per-workgroup
+    // scratch items, the blocked cells and the pairs of the two-jobs-per-lane kernels, the grid
+    struct LaunchPlan {
+        long long ops_total = 0, vsa_total = 0, dump_total = 0, max_T = 0, max_tb = 0, max_ckpt = 0, total_cells = 0;
+        long long max_runs = 0, sub_cols = 0, span_total = 0, seed_total = 0;
+        std::vector<int> sub_t, sub_q, pair_list;
+        long long grid = 0, carry_T = 0, bnd_per_wave = 0;
+    };
+    static int nbits(int v) { int b = 0; while ((1LL << b) <= v) b++; return b; }
+
     int run_impl(const ResidentSeqs &seqs, int mode, bool cont, const std::vector<JobSpec> &specs,
                  std::vector<JobOut> &out, const std::vector<RegionPoints> *pts, SeedPlan *seed = nullptr) {
-        const bool trace = c4cfg::has(c4cfg::TRACE);
-        const auto t_begin = std::chrono::steady_clock::now();
-        struct Trace {
-            bool on; std::chrono::steady_clock::time_point t0; int mode, n;
-            ~Trace() {
-                if (on) fprintf(stderr, "c4gpu trace: run mode %d jobs %d host+device %.3f ms\n", mode, n,
-                                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-            }
-        } tr{trace, t_begin, mode, (int)specs.size()};
-        auto lap = [&](const char *what) {
-            if (trace) fprintf(stderr, "c4gpu trace:   %-18s at %.3f ms\n", what,
-                               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
-        };
+        const RunTrace tr{c4cfg::has(c4cfg::TRACE), std::chrono::steady_clock::now(), mode, (int)specs.size()};
         const int n = (int)specs.size();
         // every field of entries [0, n) is rewritten after the launch; a vector that is reused for launches of very
         // different sizes (4 096 checkpoint jobs, then 778 443 sub-alignments, every step) is never shrunk: building
         // and tearing down its tail was the largest host item of such a step
         if ((int)out.size() < n) out.resize(n);
         if (!n) return 0;
-        const bool use_local = local && local_exact && !cont && (mode == MODE_SCORE || mode == MODE_REGION);
+        // -- the facts of the launch, and the kernel that serves it (c4_kernel_choice.h); the switches are read on every call
+        // so that a test can flip one
+        const Switches sw = Switches::from_config();
+        LaunchFacts f;
+        f.family = family; f.mode = mode; f.cont = cont; f.n = n; f.blocked = pts != nullptr;
+        f.local = local; f.local_exact = local_exact;
         // packed region-start slot: (query_start << tshift) | target_start must fit 31 bits for every job
-        auto nbits = [](int v) { int b = 0; while ((1LL << b) <= v) b++; return b; };
-        // C4GPU_PACK=0 forces the two-slot form (what targets beyond 2^31 / query-rows columns get): read on
-        // every call so that a test can switch it
-        bool pack = (mode == MODE_REGION) && !(c4cfg::is(c4cfg::PACK, 0));
-        for (int i = 0; i < n && pack; i++)
-            pack = nbits(specs[i].region.query_length) + nbits(specs[i].region.target_length) <= 31;
-        const int wpe_env = c4cfg::num(c4cfg::WPE, 0);
-        int span = 0;
+        f.starts_pack = mode == MODE_REGION;
+        for (int i = 0; i < n && f.starts_pack; i++)
+            f.starts_pack = nbits(specs[i].region.query_length) + nbits(specs[i].region.target_length) <= 31;
         for (int i = 0; i < n; i++) {
             const int sp = specs[i].span_in ? 1 : (specs[i].span_out ? 2 : 0);
-            if (i && sp != span) { c4h::set_error("jobs with and without span matrices in one call"); return -1; }
-            span = sp;
+            if (i && sp != f.span) { c4h::set_error("jobs with and without span matrices in one call"); return -1; }
+            f.span = sp;
         }
-        bool cont_free = false;
+        const int span = f.span;
         if (cont && (mode == MODE_PATH || mode == MODE_CKPT) && !pts && !span) {
             long long worst = 0;
             bool cells_leave = false;             // checkpoint cells handed to the caller must be the reference's in every state
@@ -406,106 +387,42 @@ struct Engine {
                 worst = std::max(worst, (long long)specs[i].region.query_length + specs[i].region.target_length);
                 cells_leave |= specs[i].dump_checkpoints;
             }
-            cont_free = !cells_leave && cont_free_ok(worst);
+            f.cont_free = !cells_leave && cont_free_ok(worst);
         }
-        const uint8_t *staged_codes = nullptr;         // set with the staged packed score pass: its residue-code table
-        const KernelInfo *ki = get_kernel(family, mode, cont, cont ? cont_free : use_local, pack, pts ? 0 : wpe_env, pts != nullptr, span);
-        if (!ki && cont_free) ki = get_kernel(family, mode, cont, false, pack, pts ? 0 : wpe_env, pts != nullptr, span);
-        if (!ki) { c4h::set_error("no compiled kernel for this model/mode"); return -1; }
-        const int span_cs = 1 + model->total_shadow_designations;
-        // whole-rectangle passes whose query spans several 64*R-row strips run on 4 cooperating waves per
-        // job (strip carry rows stay in LDS instead of HBM); C4GPU_MW=0 forces the one-wave kernels
-        const int mw_env = c4cfg::num(c4cfg::MW, 1);
+        if (seed) { f.seed_mode = seed->mode; f.kshift = seed->kshift; f.fmt16 = seed->fmt16; }
+        f.pk16_params_ok = pk16_params_ok;
+        f.pk16_all_fit = f.seed_mode == 1;
+        for (int i = 0; i < n && f.pk16_all_fit; i++) f.pk16_all_fit = pk16_fits(specs[i].region.query_length, specs[i].region.target_length);
+        f.tdense_n = seqs.tdense_n; f.ss16_built = seqs.ss16_built;
+        f.cu_count = ctx->prop.multiProcessorCount;
+        if (!cont) {
+            h_qlen.resize(n);
+            for (int i = 0; i < n; i++) h_qlen[i] = specs[i].region.query_length;
+            f.query_length = h_qlen.data(); f.n_lengths = n;
+        }
+        const KernelChoice choice = choose_kernel(f, sw);
+        if (choice.error) { c4h::set_error(choice.error); return -1; }
+        const KernelInfo *ki = choice.ki;
+        if (choice.needs_ss16 && ensure_ss16(seqs)) return -1;
         if (seed) {
-            int win_nw = seed->mode == 2 ? window_waves(family) : 4;
-            // the score pass of a launch with too few jobs to occupy the device on four waves each (256 proteins against one
-            // chromosome): eight waves of half the rows (C4GPU_MW=4 keeps four)
-            if (seed->mode == 1 && mw_env != 4 && (long long)n * 8 <= 2LL * 4 * ctx->prop.multiProcessorCount &&
-                get_kernel_mw(family, mode, true, false, 8, false, 1))
-                win_nw = 8;
-            ki = get_kernel_mw(family, mode, true, mode == MODE_REGION, win_nw, false, seed->mode);
-            if (!ki || !use_local || (mode == MODE_REGION && !pack)) { c4h::set_error("no seeded kernel for this launch"); return -1; }
-            // the score pass with dumps: two jobs per lane in packed 16-bit halves where every score fits (C4GPU_PK16=0: never)
-            const int pk_env = c4cfg::num(c4cfg::PK16, 1);
-            const KernelInfo *kpk = (seed->mode == 1 && pk_env && pk16_params_ok && n >= 2) ? get_kernel_pk16(family, pk_env == 3 ? 0 : pk_env == 4 ? 2 : 1) : nullptr;      // 3: the all-asm form (c4_viterbi16_kernel.h, VAR 0)
-            if (kpk) {
-                bool fits = true;
-                for (int i = 0; i < n && fits; i++) fits = pk16_fits(specs[i].region.query_length, specs[i].region.target_length);
-                // variant 1 reads the four splice values of a column as one packed 8-byte entry
-                if (fits && pk_env != 3 && ensure_ss16(seqs)) return -1;
-                if (fits) ki = kpk;
-                // ... and with the packed region windows behind it (c4_win16_kernel.h; C4GPU_WIN16=0: the 32-bit windows) it
-                // writes its dumps as 16-bit rows: window rows and columns must fit 15 / 16 bits
-                const int w16_env = c4cfg::num(c4cfg::WIN16, 1);
-                const KernelInfo *kd = (fits && pk_env == 1 && w16_env) ? get_kernel_pk16(family, 3) : nullptr;
-                // (the packed windows index a query profile by the targets' dense codes: at most eight residue codes in the batch)
-                if (kd && get_kernel_win16(family, 0) && seed->kshift <= 15 && seqs.tdense_n > 0) {
-                    bool rows_ok = true;
-                    for (int i = 0; i < n && rows_ok; i++) rows_ok = specs[i].region.query_length < 32000;
-                    if (rows_ok) { ki = kd; seed->fmt16 = true; }
-                    // ... and with its column loop fed from LDS alone (IO 1) where every query fits the strips of one workgroup
-                    // and the targets hold few enough residue codes for the query profile (C4GPU_PK16_IO=0: never; 1: with a barrier per chunk instead of progress counters)
-                    const int io_env = c4cfg::num(c4cfg::PK16_IO, 2);
-                    const KernelInfo *ke = (rows_ok && io_env) ? get_kernel_pk16(family, io_env == 2 ? 5 : 4) : nullptr;     // 2 (default): progress counters between the cooperating waves; 1: a barrier per chunk
-                    // seven or eight codes (IUPAC ambiguity codes in the targets): the staged form with the larger profile, where every
-                    // query fits its four strips of 256 rows (C4GPU_PK16_C8=0: the form that loads per step)
-                    if (ke && seqs.tdense_n > pk16_staged_codes() && seqs.tdense_n <= 8 && io_env == 2 &&
-                        !(c4cfg::is(c4cfg::PK16_C8, 0)) && get_kernel_pk16(family, 8)) {
-                        bool strips_ok = true;
-                        for (int i = 0; i < n && strips_ok; i++) strips_ok = specs[i].region.query_length + 1 <= pk16_staged_rows();
-                        if (strips_ok) { ki = get_kernel_pk16(family, 8); staged_codes = seqs.tdense.p; }
-                    }
-                    if (ke && seqs.tdense_n > 0 && seqs.tdense_n <= pk16_staged_codes()) {
-                        bool strips_ok = true;
-                        for (int i = 0; i < n && strips_ok; i++) strips_ok = specs[i].region.query_length + 1 <= pk16_staged_rows();
-                        if (strips_ok) { ki = ke; staged_codes = seqs.tdense.p; }
-                        else if (io_env == 2 && !(c4cfg::is(c4cfg::PK16_R6, 0))) {
-                            // queries of 1 024 .. 1 535 rows: six rows per lane put them into the four strips of one workgroup
-                            // (C4GPU_PK16_R6=0: the form that loads per step, in two passes over the target)
-                            const KernelInfo *kh = get_kernel_pk16(family, 7);
-                            bool six_ok = kh != nullptr;
-                            for (int i = 0; i < n && six_ok; i++) six_ok = specs[i].region.query_length + 1 <= pk16_staged_rows6();
-                            if (six_ok) { ki = kh; staged_codes = seqs.tdense.p; }
-                            // ... longer ones in several super-strips of that form (C4GPU_PK16_LONG=0: the per-step form)
-                            else if (get_kernel_pk16(family, 9) && !(c4cfg::is(c4cfg::PK16_LONG, 0))) {
-                                ki = get_kernel_pk16(family, 9); staged_codes = seqs.tdense.p;
-                            }
-                        }
-                        // ... on eight waves of two rows per lane where the launch has at most one pair of jobs per compute unit (the
-                        // shard of a strong-scaled run): twice the waves on the same rows (C4GPU_PK16_NW8=0: never; 1: always)
-                        const int nw8_env = c4cfg::num(c4cfg::PK16_NW8, -1);
-                        const KernelInfo *kg = (strips_ok && io_env == 2 && nw8_env != 0) ? get_kernel_pk16(family, 6) : nullptr;
-                        if (kg && (nw8_env == 1 || (n + 1) / 2 <= ctx->prop.multiProcessorCount)) ki = kg;
-                    }
-                }
-            }
+            seed->fmt16 = choice.fmt16;
             if (seed->mode == 1) { seed->seedw = ki->seedw; seed->dc = ki->max_at; }
-            if (seed->mode == 2 && seed->fmt16) {
-                const int w16_env = c4cfg::num(c4cfg::WIN16, 1);     // 2..9: one shape whatever the jobs (tests, measurement)
-                int shape = w16_env == 9 ? 0 : w16_env - 1;
-                if (w16_env <= 1) {          // the strips of a window on two cooperating waves where the first windows have two strips and more
-                    long long strips = 0;
-                    for (int i = 0; i < n; i++) strips += (specs[i].region.query_length + 1 + 255) / 256;
-                    // ... on four where the launch has at most one pair of jobs per compute unit (the shard of a strong-scaled run:
-                    // 512 pairs, region windows 30.5 -> 20.7 ms per step, profiles/r05_shard_sweep.log)
-                    shape = strips >= 2LL * n ? ((n + 1) / 2 <= ctx->prop.multiProcessorCount ? 4 : 7) : 0;
-                }
-                ki = get_kernel_win16(family, shape);
-                if (!ki || !seqs.ss16_built) { c4h::set_error("no packed window kernel for this launch"); return -1; }
-            }
-        } else if (mw_env && !cont && (mode == MODE_SCORE || mode == MODE_REGION)) {
-            const KernelInfo *kmw = get_kernel_mw(family, mode, use_local, pack, 4, pts != nullptr);
-            if (kmw) {
-                long long strips = 0;
-                for (int i = 0; i < n; i++) strips += (specs[i].region.query_length + 1 + 64 * kmw->R - 1) / (64 * kmw->R);
-                if (strips >= 3LL * n) ki = kmw;
-            }
-            // 8 waves x 2 rows per lane cover the same rows per workgroup with twice the waves: taken when the
-            // launch has too few jobs to occupy the device with 4 waves each (C4GPU_MW=4 keeps 4)
-            const KernelInfo *kmw8 = (ki == kmw && mw_env != 4 && !pts) ? get_kernel_mw(family, mode, use_local, pack, 8) : nullptr;
-            if (kmw8 && (long long)n * 8 <= 2LL * 4 * ctx->prop.multiProcessorCount) ki = kmw8;
+            if (tr.on) fprintf(stderr, "c4gpu trace:   seeded pass %d with kernel %s\n", seed->mode, ki->name);
         }
-        if (seed && c4cfg::has(c4cfg::TRACE)) fprintf(stderr, "c4gpu trace:   seeded pass %d with kernel %s\n", seed->mode, ki->name);
+        const uint8_t *staged_codes = choice.staged_codes ? seqs.tdense.p : nullptr;     // the staged packed score pass's residue-code table
+        LaunchPlan lp;
+        if (plan_jobs(specs, mode, ki, pts, span, seed, tr, lp)) return -1;
+        if (launch_jobs(seqs, mode, ki, specs, pts, span, seed, staged_codes, tr, lp)) return -1;
+        tr.lap("runs downloaded");
+        return unpack(mode, ki, n, out);
+    }
+
+    // The launch's jobs in the order the device takes them (h_order, h_jobs), their offsets into the launch's buffers and the
+    // sizes of those, the grid.
+    int plan_jobs(const std::vector<JobSpec> &specs, int mode, const KernelInfo *ki, const std::vector<RegionPoints> *pts, int span,
+                  SeedPlan *seed, const RunTrace &tr, LaunchPlan &lp) {
+        const int n = (int)specs.size();
+        const int span_cs = 1 + model->total_shadow_designations;
         // longest first (persistent waves pull from the queue head)
         std::vector<int> &order = h_order;
         order.resize(n);
@@ -527,10 +444,7 @@ struct Engine {
         }
         std::vector<DevJob> &jobs = h_jobs;
         jobs.resize(n);
-        long long ops_total = 0, vsa_total = 0, dump_total = 0, max_T = 0, max_tb = 0, max_ckpt = 0, total_cells = 0;
-        long long max_runs = 0, sub_cols = 0, span_total = 0, seed_total = 0;
         if (seed && seed->mode == 1) seed->off.assign(n, -1);
-        std::vector<int> sub_t, sub_q;
         // the fields that do not depend on the jobs before it ...
         parallel_for(n, 32768, [&](long long first, long long last) {
             for (long long x = first; x < last; x++) {
@@ -553,20 +467,20 @@ struct Engine {
             const JobSpec &s = specs[order[x]];
             DevJob &j = jobs[x];
             if (span) {
-                j.span_off = span_total;
-                span_total += (long long)(s.region.query_length + 1) * (s.region.target_length + 1) * span_cs;
+                j.span_off = lp.span_total;
+                lp.span_total += (long long)(s.region.query_length + 1) * (s.region.target_length + 1) * span_cs;
             }
             if (pts) {
                 const RegionPoints &rp = (*pts)[order[x]];
-                j.sub_off = sub_cols; j.sub_pt_off = (int)sub_t.size(); j.sub_pt_n = (int)rp.size();
-                sub_cols += s.region.target_length + 2;
-                for (const auto &p : rp) { sub_t.push_back(p.first); sub_q.push_back(p.second); }
+                j.sub_off = lp.sub_cols; j.sub_pt_off = (int)lp.sub_t.size(); j.sub_pt_n = (int)rp.size();
+                lp.sub_cols += s.region.target_length + 2;
+                for (const auto &p : rp) { lp.sub_t.push_back(p.first); lp.sub_q.push_back(p.second); }
             }
             if (seed) {
                 if (seed->mode == 1) {            // dumps d = 1 .. T >> kshift, two columns of Q + 1 rows each
-                    j.seed_off = seed_total; j.seed_rows = s.region.query_length + 1;
-                    seed->off[order[x]] = seed_total;
-                    seed_total += (long long)(s.region.target_length >> seed->kshift) * ki->max_at * (s.region.query_length + 1) *
+                    j.seed_off = lp.seed_total; j.seed_rows = s.region.query_length + 1;
+                    seed->off[order[x]] = lp.seed_total;
+                    lp.seed_total += (long long)(s.region.target_length >> seed->kshift) * ki->max_at * (s.region.query_length + 1) *
                                   ki->seedw;
                 } else {
                     j.seed_off = seed->off[order[x]]; j.seed_rows = seed->rows[order[x]];
@@ -576,91 +490,101 @@ struct Engine {
                     }
                 }
             }
-            j.ops_off = ops_total; j.ops_cap = 0; j.vsa_off = (int)vsa_total;
-            total_cells += (long long)(j.Q + 1) * (j.T + 1);
-            max_T = std::max<long long>(max_T, j.T);
+            j.ops_off = lp.ops_total; j.ops_cap = 0; j.vsa_off = (int)lp.vsa_total;
+            lp.total_cells += (long long)(j.Q + 1) * (j.T + 1);
+            lp.max_T = std::max<long long>(lp.max_T, j.T);
             if (mode == MODE_PATH) {
                 const long long strips = (j.Q + 1 + 64 * ki->R - 1) / (64 * ki->R);
                 j.ops_cap = 3 * (j.Q + j.T) + 16;
-                max_runs = std::max<long long>(max_runs, j.ops_cap);
-                ops_total += j.ops_cap;
-                max_tb = std::max(max_tb, strips * (long long)(j.T + 64) * 64 * ki->R);
+                lp.max_runs = std::max<long long>(lp.max_runs, j.ops_cap);
+                lp.ops_total += j.ops_cap;
+                lp.max_tb = std::max(lp.max_tb, strips * (long long)(j.T + 64) * 64 * ki->R);
             }
             if (mode == MODE_CKPT) {
                 const long long ck = (long long)j.cp_count * ki->max_at * (j.Q + 1) * ki->n_states * ki->cs;
-                max_ckpt = std::max(max_ckpt, ck);
-                vsa_total += j.cp_count + 1;
-                if (s.dump_checkpoints) { j.ckpt_off = dump_total; dump_total += ck; }
+                lp.max_ckpt = std::max(lp.max_ckpt, ck);
+                lp.vsa_total += j.cp_count + 1;
+                if (s.dump_checkpoints) { j.ckpt_off = lp.dump_total; lp.dump_total += ck; }
             }
         }
         // windows chained on the device: a later window of a job spans one dump interval plus the dumped columns, which can be
         // more than every FIRST window of the launch: the strip carry rows are laid out for the longest window any hop can have
         if (seed && seed->mode == 2 && seed->hops)
-            max_T = std::max<long long>(max_T, (1LL << seed->kshift) + 2LL * ki->max_at);
-        lap("jobs built");
+            lp.max_T = std::max<long long>(lp.max_T, (1LL << seed->kshift) + 2LL * ki->max_at);
+        tr.lap("jobs built");
         // persistent grid: as many waves as the device keeps resident, bounded by the scratch it implies
         int blocks_per_cu = 0;
         HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, ki->func, 64 * ki->waves, 0));
         if (blocks_per_cu < 1) blocks_per_cu = 1;
-        if (trace) fprintf(stderr, "c4gpu trace:   kernel %s: %d workgroups per CU\n", ki->name, blocks_per_cu);
+        if (tr.on) fprintf(stderr, "c4gpu trace:   kernel %s: %d workgroups per CU\n", ki->name, blocks_per_cu);
         // the kernels that run two jobs per lane in pairs the host lists: neighbours of the same root
-        std::vector<int> pair_list;
         if (ki->pairs)
             for (int x = 0; x < n;) {
                 const bool two = x + 1 < n && jobs[x + 1].root == jobs[x].root;
-                pair_list.push_back(x); pair_list.push_back(two ? x + 1 : -1);
+                lp.pair_list.push_back(x); lp.pair_list.push_back(two ? x + 1 : -1);
                 x += two ? 2 : 1;
             }
-        long long grid = std::min<long long>(ki->pairs ? (long long)pair_list.size() / 2 : n, (long long)blocks_per_cu * ctx->prop.multiProcessorCount);
+        lp.grid = std::min<long long>(ki->pairs ? (long long)lp.pair_list.size() / 2 : n, (long long)blocks_per_cu * ctx->prop.multiProcessorCount);
         // strip carry rows in HBM are only needed when a job has more strips than one workgroup holds at once
         // (one for the single-wave kernels, `waves` for the cooperating ones)
-        long long carry_T = 0;
         for (int x = 0; x < n; x++)
-            if ((jobs[x].Q + 1 + 64 * ki->R - 1) / (64 * ki->R) > (ki->hbm_carry ? 1 : ki->waves)) carry_T = max_T;
+            if ((jobs[x].Q + 1 + 64 * ki->R - 1) / (64 * ki->R) > (ki->hbm_carry ? 1 : ki->waves)) lp.carry_T = lp.max_T;
         // per workgroup: one "empty" column (what the first strip reads as its row above) + two carry rows
-        const long long bnd_per_wave = (2 * ((carry_T ? carry_T : 0) + 1) + 1) * (long long)std::max(ki->bnd, 1);
-        const long long bytes_per_wave = bnd_per_wave * 4 + max_tb * 4 + max_ckpt * 4 + max_runs * 4;
+        lp.bnd_per_wave = (2 * ((lp.carry_T ? lp.carry_T : 0) + 1) + 1) * (long long)std::max(ki->bnd, 1);
+        const long long bytes_per_wave = lp.bnd_per_wave * 4 + lp.max_tb * 4 + lp.max_ckpt * 4 + lp.max_runs * 4;
+        const long long budget = (long long)(ctx->prop.totalGlobalMem / 4);
+        if (bytes_per_wave * lp.grid > budget) lp.grid = std::max<long long>(1, budget / std::max<long long>(1, bytes_per_wave));
+        return 0;
+    }
+
+    // Uploads what plan_jobs laid out, launches, downloads the results; a launch whose traceback runs overflow the compact run
+    // array is repeated once with the worst case.  Leaves the results in h_res, h_runs, h_vsa, h_dump.
+    int launch_jobs(const ResidentSeqs &seqs, int mode, const KernelInfo *ki, const std::vector<JobSpec> &specs,
+                    const std::vector<RegionPoints> *pts, int span, SeedPlan *seed, const uint8_t *staged_codes, const RunTrace &tr,
+                    LaunchPlan &lp) {
+        const int n = (int)specs.size();
+        const int span_cs = 1 + model->total_shadow_designations;
+        const std::vector<int> &order = h_order;
+        const std::vector<DevJob> &jobs = h_jobs;
+        hipStream_t s = ctx->stream;
         // compact run array: paths are mostly long runs, so a fraction of the worst case is plenty; a
         // launch that overflows it is repeated with the worst case
-        long long runs_capacity = std::min<long long>(ops_total, std::max<long long>(1 << 20, (long long)n * 256));
-        const long long budget = (long long)(ctx->prop.totalGlobalMem / 4);
-        if (bytes_per_wave * grid > budget) grid = std::max<long long>(1, budget / std::max<long long>(1, bytes_per_wave));
-        hipStream_t s = ctx->stream;
+        long long runs_capacity = std::min<long long>(lp.ops_total, std::max<long long>(1 << 20, (long long)n * 256));
         std::vector<DevResult> &res = h_res;
         res.resize(n);
         std::vector<uint32_t> &runs = h_runs;
         runs.clear();
         std::vector<DevVsa> &vsa = h_vsa;         // kept between launches: fresh vectors of this size are zeroed and
         std::vector<int> &dump = h_dump;          // page-faulted in on every call (50 MB for a C2-shaped batch)
-        vsa.resize(vsa_total);
-        dump.resize(dump_total);
+        vsa.resize(lp.vsa_total);
+        dump.resize(lp.dump_total);
         for (int attempt = 0; attempt < 2; attempt++) {
             int zero = 0;
             unsigned long long zero64 = 0;
             if (d_jobs.upload(jobs.data(), n, s) || d_results.alloc(n) || d_queue.upload(&zero, 1, s) ||
-                d_runs_used.upload(&zero64, 1, s) || d_bnd.alloc(bnd_per_wave * grid) || d_vsa.alloc(vsa_total) ||
-                d_runs.alloc(max_runs * grid) || d_runs_out.alloc(runs_capacity) ||
-                d_tb.alloc(max_tb * grid) || d_ckpt.alloc(max_ckpt * grid) || d_ckpt_dump.alloc(dump_total))
+                d_runs_used.upload(&zero64, 1, s) || d_bnd.alloc(lp.bnd_per_wave * lp.grid) || d_vsa.alloc(lp.vsa_total) ||
+                d_runs.alloc(lp.max_runs * lp.grid) || d_runs_out.alloc(runs_capacity) ||
+                d_tb.alloc(lp.max_tb * lp.grid) || d_ckpt.alloc(lp.max_ckpt * lp.grid) || d_ckpt_dump.alloc(lp.dump_total))
                 return -1;
             LaunchArgs a;
             a.kp = kparams.p; a.seqs = seqs.dev; a.jobs = d_jobs.p; a.n_jobs = n; a.results = d_results.p;
             a.seqs.sub_colptr = nullptr; a.seqs.sub_rows = nullptr;
             a.seqs.span_in = nullptr; a.seqs.span_out = nullptr;
             if (span) {                                      // matrices of all jobs, in job order
-                std::vector<int> host(span_total);
+                std::vector<int> host(lp.span_total);
                 for (int x = 0; x < n; x++) {
                     const JobSpec &sp = specs[order[x]];
                     const int32_t *src = span == 1 ? sp.span_in : sp.span_out;
                     const long long cnt = (long long)(jobs[x].Q + 1) * (jobs[x].T + 1) * span_cs;
                     memcpy(host.data() + jobs[x].span_off, src, sizeof(int) * cnt);
                 }
-                if (d_span.upload(host.data(), span_total, s)) return -1;
+                if (d_span.upload(host.data(), lp.span_total, s)) return -1;
                 a.seqs.span_in = d_span.p; a.seqs.span_out = d_span.p;
             }
             if (pts) {
-                sub_q.push_back(0);                      // the kernels' row prefetch may touch one entry past the last list
-                if (d_sub_t.upload(sub_t.data(), sub_t.size(), s) || d_sub_q.upload(sub_q.data(), sub_q.size(), s) ||
-                    d_sub_colptr.alloc(2 * sub_cols)) return -1;
+                lp.sub_q.push_back(0);                      // the kernels' row prefetch may touch one entry past the last list
+                if (d_sub_t.upload(lp.sub_t.data(), lp.sub_t.size(), s) || d_sub_q.upload(lp.sub_q.data(), lp.sub_q.size(), s) ||
+                    d_sub_colptr.alloc(2 * lp.sub_cols)) return -1;
                 hipLaunchKernelGGL(subopt_colptr_kernel, dim3(std::min(n, 65535)), dim3(256), 0, s, d_jobs.p, n,
                                    d_sub_t.p, d_sub_q.p, d_sub_colptr.p);
                 HIP_OK(hipGetLastError());
@@ -675,48 +599,48 @@ struct Engine {
             }
             a.seqs.seed = nullptr;
             if (seed) {
-                if (seed->mode == 1 && d_seed.alloc((size_t)std::max<long long>(seed_total, 1))) return -1;
+                if (seed->mode == 1 && d_seed.alloc((size_t)std::max<long long>(lp.seed_total, 1))) return -1;
                 a.seqs.seed = d_seed.p;
             }
-            a.vsas = d_vsa.p; a.ops = nullptr; a.queue = d_queue.p; a.grid = (int)grid; a.stream = s;
+            a.vsas = d_vsa.p; a.ops = nullptr; a.queue = d_queue.p; a.grid = (int)lp.grid; a.stream = s;
             if (ki->pairs) {
-                if (d_pairs.upload(pair_list.data(), pair_list.size(), s)) return -1;
-                a.aux = d_pairs.p; a.n_aux = (int)(pair_list.size() / 2);
+                if (d_pairs.upload(lp.pair_list.data(), lp.pair_list.size(), s)) return -1;
+                a.aux = d_pairs.p; a.n_aux = (int)(lp.pair_list.size() / 2);
             }
             if (staged_codes) a.aux = reinterpret_cast<const int *>(staged_codes);
-            a.scratch.bnd = d_bnd.p; a.scratch.bnd_stride = bnd_per_wave; a.scratch.carry = carry_T ? 1 : 0;
-            a.scratch.tb = max_tb ? d_tb.p : nullptr; a.scratch.tb_stride = max_tb;
-            a.scratch.ckpt = max_ckpt ? d_ckpt.p : nullptr; a.scratch.ckpt_stride = max_ckpt;
+            a.scratch.bnd = d_bnd.p; a.scratch.bnd_stride = lp.bnd_per_wave; a.scratch.carry = lp.carry_T ? 1 : 0;
+            a.scratch.tb = lp.max_tb ? d_tb.p : nullptr; a.scratch.tb_stride = lp.max_tb;
+            a.scratch.ckpt = lp.max_ckpt ? d_ckpt.p : nullptr; a.scratch.ckpt_stride = lp.max_ckpt;
             a.scratch.ckpt_dump = d_ckpt_dump.p;
-            a.scratch.runs = d_runs.p; a.scratch.runs_stride = max_runs;
+            a.scratch.runs = d_runs.p; a.scratch.runs_stride = lp.max_runs;
             a.scratch.runs_out = d_runs_out.p; a.scratch.runs_capacity = runs_capacity;
             a.scratch.runs_used = d_runs_used.p;
-            lap("uploaded");
+            tr.lap("uploaded");
             if (ctx->timing) HIP_OK(hipEventRecord(ctx->ev0, s));
             HIP_OK(ki->launch(a));
             if (ctx->timing) HIP_OK(hipEventRecord(ctx->ev1, s));
             unsigned long long used = 0;
             if (d_results.download(res.data(), n, s) || d_runs_used.download(&used, 1, s) ||
-                d_vsa.download(vsa.data(), vsa_total, s) || d_ckpt_dump.download(dump.data(), dump_total, s))
+                d_vsa.download(vsa.data(), lp.vsa_total, s) || d_ckpt_dump.download(dump.data(), lp.dump_total, s))
                 return -1;
             HIP_OK(c4_stream_sync(s));
-            lap("kernel + results");
+            tr.lap("kernel + results");
             if (ctx->timing) {
                 float ms = 0;
                 HIP_OK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-                ctx->kernel_ms[mode] += ms; ctx->kernel_launches[mode]++; ctx->kernel_cells[mode] += total_cells;
+                ctx->kernel_ms[mode] += ms; ctx->kernel_launches[mode]++; ctx->kernel_cells[mode] += lp.total_cells;
             }
             if ((long long)used > runs_capacity) {          // rare: paths with very short runs
                 if (attempt == 1) { c4h::set_error("traceback runs exceed their worst-case buffer"); return -1; }
-                runs_capacity = ops_total;
+                runs_capacity = lp.ops_total;
                 continue;
             }
             runs.resize(used);
             if (d_runs_out.download(runs.data(), used, s)) return -1;
             HIP_OK(c4_stream_sync(s));
             if (span == 2) {                                 // END cells back into the callers' matrices
-                std::vector<int> host(span_total);
-                if (d_span.download(host.data(), span_total, s)) return -1;
+                std::vector<int> host(lp.span_total);
+                if (d_span.download(host.data(), lp.span_total, s)) return -1;
                 HIP_OK(c4_stream_sync(s));
                 for (int x = 0; x < n; x++) {
                     const long long cnt = (long long)(jobs[x].Q + 1) * (jobs[x].T + 1) * span_cs;
@@ -725,7 +649,16 @@ struct Engine {
             }
             break;
         }
-        lap("runs downloaded");
+        return 0;
+    }
+
+    // the results of launch_jobs, per job, into the caller's order
+    int unpack(int mode, const KernelInfo *ki, int n, std::vector<JobOut> &out) {
+        const std::vector<int> &order = h_order, &dump = h_dump;
+        const std::vector<DevJob> &jobs = h_jobs;
+        const std::vector<DevResult> &res = h_res;
+        const std::vector<uint32_t> &runs = h_runs;
+        const std::vector<DevVsa> &vsa = h_vsa;
         std::atomic<int> overflow{0};
         parallel_for(n, 32768, [&](long long first, long long last) {
             for (long long x = first; x < last; x++) {
@@ -748,4 +681,3 @@ struct Engine {
         return 0;
     }
 };
-

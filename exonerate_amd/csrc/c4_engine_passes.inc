@@ -102,7 +102,8 @@ int fused_reduced_paths(Engine &eng, const ResidentSeqs &seqs, const std::vector
     const int n = (int)red.size();
     if (!n || eng.pair_sub) return 0;
     if (c4cfg::is(c4cfg::FUSED, 0)) return 0;
-    const int wpe_env = c4cfg::num(c4cfg::WPE, 0);
+    const Switches sw = Switches::from_config();         // (read on every call: a test switches them)
+    const int wpe_env = sw.wpe;
     long long worst = 0;
     for (int i : red) worst = std::max(worst, (long long)plan[i].ar.query_length + plan[i].ar.target_length);
     const bool cont_free = eng.cont_free_ok(worst);              // the sub-alignments lie inside their pair's region
@@ -114,13 +115,10 @@ int fused_reduced_paths(Engine &eng, const ResidentSeqs &seqs, const std::vector
     // the packed 16-bit checkpoint kernel (c4_ckpt16_kernel.h: two jobs per lane) for every job whose scores, checkpoint
     // payloads and intron lengths fit its halves — in its rooted form (the component of the state the path's END is entered
     // from: one strand of est2genome) where the region pass reported that state, else over every inner state;
-    // C4GPU_CK16=0: never, 2..8: one shape whatever the jobs (tests, measurement), C4GPU_CK16_ROOT=0: never the rooted form (read on every
-    // call: a test switches them)
-    const int ck_env = c4cfg::num(c4cfg::CK16, 1);
-    const bool ck_root_env = !(c4cfg::is(c4cfg::CK16_ROOT, 0));
-    const bool ck16_on = ck_env > 0 && cont_free && eng.pk16_params_ok && seqs.tdense_n > 0;      // (dense target codes: Prof16)
-    const KernelInfo *kc16 = ck16_on ? get_kernel_ck16(eng.family, 0, false) : nullptr;
-    const KernelInfo *kc16r = (ck16_on && ck_root_env) ? get_kernel_ck16(eng.family, ck_env == 8 ? 0 : ck_env - 1, true) : nullptr;   // 1: chosen below, 8: variant 0
+    // C4GPU_CK16=0: never, 2..: one shape whatever the jobs (tests, measurement), C4GPU_CK16_ROOT=0: never the rooted form
+    const bool ck16_on = sw.ck16 > 0 && cont_free && eng.pk16_params_ok && seqs.tdense_n > 0;      // (dense target codes: Prof16)
+    const KernelInfo *kc16 = ck16_on ? get_kernel_ck16(eng.family, CK16_R4W2) : nullptr;
+    const KernelInfo *kc16r = (ck16_on && sw.ck16_root) ? get_kernel_ck16(eng.family, CK16R_R6W2) : nullptr;   // its shape: chosen below
     const int ck16_tmax = c4cfg::num(c4cfg::CK16_TMAX, 0x7fffffff);      // test hook
     hipStream_t s = ctx->stream;
     const c4h::MemRule rule{m->max_query_advance, m->max_target_advance, m->n_states, m->total_shadow_designations};
@@ -150,24 +148,15 @@ int fused_reduced_paths(Engine &eng, const ResidentSeqs &seqs, const std::vector
         }
     if (!count_g[1] && !count_g[2]) { kc16 = nullptr; kc16r = nullptr; }
     const int n16r = count_g[2], n16a = count_g[1], n16 = n16r + n16a;
-    if (kc16r && n16r && ck_env == 1) {
-        // the shape by the strips of 256 rows the rooted jobs have: four (two) cooperating waves per pair of jobs where the
-        // jobs fill them -- the launch then lasts as long as its work, not as its longest job's strips one after the other
-        // (north-star batch, two lanes: 481 -> 446 ms per step; profiles/r04_ck16_sweep.log) --, one wave per pair of short queries
-        long long strips = 0;
+    if (kc16r && n16r) {
+        long long strips = 0;                            // of 256 rows, over the rooted jobs
         int rows_max = 0;
         for (int x = 0; x < n; x++)
             if (group[x] == 2) {
                 strips += (plan[red[x]].ar.query_length + 1 + 255) / 256;
                 rows_max = std::max(rows_max, plan[red[x]].ar.query_length + 1);
             }
-        // (the four-wave shape at three waves per SIMD, 168 registers: 65 -> 52 ms per launch, step 436 -> 430 ms;
-        // profiles/r04_ck16_w3_sweep.log)
-        kc16r = get_kernel_ck16(eng.family, strips >= 3LL * n16r ? 8 : strips >= 2LL * n16r ? 5 : 0, true);
-        // regions of 1 025 .. 1 152 rows are five strips of 256 -- a second round for one wave of four -- and three strips of
-        // 384: the six-rows-per-lane shape on three waves takes them in one round (cDNAs of 1.1 kb)
-        if (rows_max > 1024 && rows_max <= 3 * 384 && strips >= 4LL * n16r && get_kernel_ck16(eng.family, 6, true))
-            kc16r = get_kernel_ck16(eng.family, 6, true);
+        kc16r = get_kernel_ck16(eng.family, choose_ck16_rooted_shape(eng.family, strips, n16r, rows_max, sw));
     }
     if (n16 && eng.ensure_ss16(seqs)) return -1;
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) {

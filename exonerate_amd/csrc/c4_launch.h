@@ -72,21 +72,13 @@ const KernelInfo *get_kernel(int family, int mode, bool cont, bool local, bool p
 // starts from a dump and reports its corner cell); local, 4 waves only
 const KernelInfo *get_kernel_mw(int family, int mode, bool local, bool pack, int waves = 4, bool sub = false, int seed = 0);
 
-// the packed 16-bit score pass with column dumps (c4_viterbi16_kernel.h): two jobs per lane; NULL = not compiled for the family.
-// Launched over the same job / result arrays as the 32-bit kernel (workgroup p runs jobs 2p and 2p + 1).
-const KernelInfo *get_kernel_pk16(int family, int variant = 0);
-// the packed 16-bit checkpoint pass (c4_ckpt16_kernel.h): two jobs per lane, one wave per pair of jobs (LaunchArgs::aux);
-// scratch.ckpt holds two slabs of ckpt_stride ints per wave; rooted: the form that computes the component of DevJob::root only
-// (NULL where the family's components overlap); variant: rows per lane / register cap shapes kept for measurement (0 = the default)
-const KernelInfo *get_kernel_ck16(int family, int variant = 0, bool rooted = false);
-// the packed 16-bit region windows (c4_win16_kernel.h): two windows per lane, one wave per pair of window chains, started from
-// the 16-bit dumps of get_kernel_pk16(family, 3); variant: rows per lane / register cap shapes (0 = the default)
-const KernelInfo *get_kernel_win16(int family, int variant = 0);
-// the staged form of the packed score pass (get_kernel_pk16(family, 4)): residue codes its query profile holds, query rows
-// (Q + 1) a workgroup covers
+// (the packed 16-bit passes' kernels -- get_kernel_pk16, get_kernel_ck16, get_kernel_win16 -- are listed by named form in
+// c4_kernel_choice.h)
+// the staged forms of the packed score pass: residue codes the query profile of PK16_STAGED holds, query rows (Q + 1) a
+// workgroup of it covers, ... and one of the six-rows-per-lane form (PK16_STAGED_R6)
 int pk16_staged_codes();
 int pk16_staged_rows();
-int pk16_staged_rows6();            // ... of the six-rows-per-lane form (get_kernel_pk16 variant 7)
+int pk16_staged_rows6();
 hipError_t pk16_build_splice(int family, const KParams *kp, const int *ss, long long ss_stride, long long n, void *out, hipStream_t s);
 
 #define C4K_DEFINE_KERNEL_SPAN(SYMBOL, M, RVAL, MODE, CONT, LOCAL, PACK, WPE, SUBV, SPANV)                                          \

@@ -1,6 +1,6 @@
 // the packed 16-bit region windows (c4_win16_kernel.h): two windows per lane, one wave per pair of window chains.  est2genome
 // only (the family the packed score pass serves: the windows start from its 16-bit dumps).
-#include "../c4_launch.h"
+#include "../c4_kernel_choice.h"
 #include "../c4_win16_kernel.h"
 namespace c4k {
 #define WIN16_KERNEL(NAME, M, RV, WPEV, NWV)                                                                            \
@@ -21,17 +21,17 @@ WIN16_KERNEL(kwin16_est2genome_r2w4n8, Est2GenomeDesc, 2, 4, 8)
 WIN16_KERNEL(kwin16_est2genome_r2w4n4, Est2GenomeDesc, 2, 4, 4)
 WIN16_KERNEL(kwin16_est2genome_r4w2n2, Est2GenomeDesc, 4, 2, 2)
 WIN16_KERNEL(kwin16_est2genome_r4w3n2, Est2GenomeDesc, 4, 3, 2)
-const KernelInfo *get_kernel_win16(int family, int variant) {
+const KernelInfo *get_kernel_win16(int family, Win16Shape shape) {
     if (family != FAM_EST2GENOME) return nullptr;
-    switch (variant) {
-        case 1: return &kwin16_est2genome_r3w3;
-        case 2: return &kwin16_est2genome_r2w4;
-        case 3: return &kwin16_est2genome_r6w2;
-        case 4: return &kwin16_est2genome_r4w2n4;
-        case 5: return &kwin16_est2genome_r2w4n8;
-        case 6: return &kwin16_est2genome_r2w4n4;
-        case 7: return &kwin16_est2genome_r4w2n2;
-        case 9: return &kwin16_est2genome_r4w3n2;
+    switch (shape) {
+        case WIN16_R3W3: return &kwin16_est2genome_r3w3;
+        case WIN16_R2W4: return &kwin16_est2genome_r2w4;
+        case WIN16_R6W2: return &kwin16_est2genome_r6w2;
+        case WIN16_R4W2N4: return &kwin16_est2genome_r4w2n4;
+        case WIN16_R2W4N8: return &kwin16_est2genome_r2w4n8;
+        case WIN16_R2W4N4: return &kwin16_est2genome_r2w4n4;
+        case WIN16_R4W2N2: return &kwin16_est2genome_r4w2n2;
+        case WIN16_R4W3N2: return &kwin16_est2genome_r4w3n2;
         default: return &kwin16_est2genome_r4w2;
     }
 }
