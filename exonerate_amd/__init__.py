@@ -418,6 +418,40 @@ class Engine:
             raise _err("c4gpu_hsp_extend_chains")
         return [out[i].aslist() for i in range(n)]
 
+    def hsp_extend_masked(self, params, match, pairs, seedlen, dropoff, seeds, mask_query, mask_target, threshold):
+        """The two-stage extension of soft-masked sets (hspset.c:981-995, c4gpu_hsp_extend_batch_masked): per seed
+        ([query_start, target_start, length, score, cobs], dropped).  A dropped seed (below `threshold` after the extension
+        that stops at masked positions) carries its masked-extended HSP."""
+        arr, keep = _pairs(pairs)
+        kind = {"dna2dna": _abi.MATCH_DNA2DNA, "protein2protein": _abi.MATCH_PROTEIN2PROTEIN,
+                "protein2dna": _abi.MATCH_PROTEIN2DNA}[match]
+        n = len(seeds)
+        cs = (_abi.HspSeed * max(1, n))(*[_abi.HspSeed(*s) for s in seeds])
+        out = (_abi.Hsp * max(1, n))()
+        dropped = (C.c_int32 * max(1, n))()
+        if _lib().c4gpu_hsp_extend_batch_masked(self.ctx, params, kind, arr, len(pairs), seedlen, dropoff, int(bool(mask_query)),
+                                                int(bool(mask_target)), threshold, cs, n, out, dropped) != 0:
+            raise _err("c4gpu_hsp_extend_batch_masked")
+        return [(out[i].aslist(), int(dropped[i])) for i in range(n)]
+
+    def hsp_extend_chains_masked(self, params, match, pairs, seedlen, dropoff, seeds, chain, horizon0, mask_query, mask_target,
+                                 threshold):
+        """The same with the diagonal horizon applied on the device (c4gpu_hsp_extend_chains_masked): a skipped seed comes
+        back with length -1 and dropped 0; a dropped seed moves its chain's horizon to its masked end."""
+        arr, keep = _pairs(pairs)
+        kind = {"dna2dna": _abi.MATCH_DNA2DNA, "protein2protein": _abi.MATCH_PROTEIN2PROTEIN,
+                "protein2dna": _abi.MATCH_PROTEIN2DNA}[match]
+        n, nc = len(seeds), len(horizon0)
+        cs = (_abi.HspSeed * max(1, n))(*[_abi.HspSeed(*s) for s in seeds])
+        cc = (C.c_int32 * max(1, n))(*chain)
+        h0 = (C.c_int32 * max(1, nc))(*horizon0)
+        out = (_abi.Hsp * max(1, n))()
+        dropped = (C.c_int32 * max(1, n))()
+        if _lib().c4gpu_hsp_extend_chains_masked(self.ctx, params, kind, arr, len(pairs), seedlen, dropoff, int(bool(mask_query)),
+                                                 int(bool(mask_target)), threshold, cs, n, cc, nc, h0, out, dropped) != 0:
+            raise _err("c4gpu_hsp_extend_chains_masked")
+        return [(out[i].aslist(), int(dropped[i])) for i in range(n)]
+
     def sdp(self, model, pairs, hsps, query_advance=1, target_advance=1, dropoff=50, threshold=100, max_alignments=4):
         """The reference's default gapped-extension heuristic (SDP, GAM_Result_SDP_create gam.c:852) for a batch: per pair
         the list of alignments found from its HSPs ([query_start, target_start, length, score, cobs] each), both

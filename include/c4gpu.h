@@ -14,6 +14,7 @@
  *   c4gpu_alignment_format   <->  Alignment_print_{sugar,cigar,vulgar}_block  src/c4/alignment.c:1622-1779
  *   c4gpu_hsp_extend_batch   <->  HSPset_seed_hsp (HSP_trim_ends/_init/_extend) src/comparison/hspset.c:933-997
  *   c4gpu_hsp_extend_chains  <->  the same with its horizon test              src/comparison/hspset.c:939-958,990
+ *   c4gpu_hsp_extend_{batch,chains}_masked  <->  the same for soft-masked alphabets (two stages)  src/comparison/hspset.c:981-995
  *   c4gpu_alignment_display / _format_gff / _format_ryo  <->  Alignment_display / _display_gff / _display_ryo  src/c4/alignment.c:1343,3212,2659
  *   c4gpu_batch_run_regions  <->  Optimal_find_path with a region (--refine)   src/hub/gam.c:605-655
  *   c4gpu_seed_scan          <->  Seeder_add_target's automaton walk src/comparison/seeder.c:649-720,852-915
@@ -471,6 +472,30 @@ int         c4gpu_hsp_extend_chains(c4gpu_ctx *ctx, const c4gpu_params *params, 
                                     const c4gpu_pair *pairs, int32_t n_pairs, int32_t seedlen, int32_t dropoff,
                                     const c4gpu_hsp_seed *seeds, int32_t n_seeds, const int32_t *chain, int32_t n_chains,
                                     const int32_t *horizon0, c4gpu_hsp *out);
+
+/* Soft-masked sets (--softmaskquery / --softmasktarget): the two-stage rule of HSPset_seed_hsp (hspset.c:981-995).
+ * mask_query / mask_target: is that side's alphabet soft-masked (Alphabet.is_soft_masked); a lower-case residue on a side
+ * whose flag is 0 is NOT masked (Alphabet_is_masked, alphabet.h:87).  On a flagged side a position is masked when its symbol
+ * is lower case and not the wildcard itself ('n' for DNA, 'x' for protein: alphabet.c:124-129 maps those where TO_UPPER does);
+ * a PROTEIN2DNA target position when any of its three bases is (match.c:212-220).  threshold: HSP_Param.threshold.
+ *   stage 1  HSP_extend(forbid_masked = TRUE) (hspset.c:762-765,794-797): each direction stops in front of the first masked
+ *            position.  If the score is then below `threshold` the seed is DROPPED: dropped[k] = 1 and out[k] holds the
+ *            masked-extended HSP (query_start, target_start, length, score; cobs = 0).  Nothing is stored for it, and the
+ *            diagonal's horizon becomes target_start + length * target advance of THAT HSP (hspset.c:985-989).
+ *   stage 2  otherwise HSP_extend(FALSE) from the ends stage 1 reached (hspset.c:992): dropped[k] = 0, out[k] as above.
+ * The encoding, for both calls: dropped[k] = 1 -- dropped, out[k] is the masked end; dropped[k] = 0 and out[k].length >= 0
+ * -- kept; dropped[k] = 0 and out[k].length = -1 -- skipped under the horizon (chains only), as in c4gpu_hsp_extend_chains.
+ * In the chain form a dropped seed moves the running horizon to its masked end, a kept one to its HSP's target end.
+ * With both flags 0 these are the two calls above (and dropped[] is all 0: the threshold stays with the caller there). */
+int         c4gpu_hsp_extend_batch_masked(c4gpu_ctx *ctx, const c4gpu_params *params, int match_type,
+                                          const c4gpu_pair *pairs, int32_t n_pairs, int32_t seedlen, int32_t dropoff,
+                                          int32_t mask_query, int32_t mask_target, int32_t threshold,
+                                          const c4gpu_hsp_seed *seeds, int32_t n_seeds, c4gpu_hsp *out, int32_t *dropped);
+int         c4gpu_hsp_extend_chains_masked(c4gpu_ctx *ctx, const c4gpu_params *params, int match_type,
+                                           const c4gpu_pair *pairs, int32_t n_pairs, int32_t seedlen, int32_t dropoff,
+                                           int32_t mask_query, int32_t mask_target, int32_t threshold,
+                                           const c4gpu_hsp_seed *seeds, int32_t n_seeds, const int32_t *chain, int32_t n_chains,
+                                           const int32_t *horizon0, c4gpu_hsp *out, int32_t *dropped);
 
 
 /* The seeder's word scan (Seeder_add_target -> FSM_traverse / Seeder_VFSM_traverse_single -> Seeder_FSM_traverse_func,

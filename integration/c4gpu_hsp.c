@@ -10,9 +10,14 @@
  * replayed in seed order: horizon test on the set's own horizon array (hspset.c:952-958), HSPset_add_known_hsp
  * (hspset.c:999: HSP_init + HSP_store, i.e. score, threshold, filter queues exactly as the reference) and the horizon
  * update.  The HSP lists that reach BSDP / SDP are the reference's, HSP for HSP.
- * Not taken: soft-masked sequences (--softmaskquery / --softmasktarget: the two-stage extension differs), --seedrepeat > 1, HSPsets without a horizon, match types other
- * than DNA / protein / protein-vs-DNA: those sets keep the reference's own function.
- * C4GPU_HSP_HOST=1 (CPU test of the seam): the extensions come from the reference's own HSPset_seed_hsp on scratch sets. */
+ * Soft-masked sets (--softmaskquery / --softmasktarget) take the two-stage rule of hspset.c:981-995 on the device
+ * (c4gpu_hsp_extend_batch_masked / _chains_masked): a seed whose masked extension stays below the threshold is DROPPED, the
+ * replay stores nothing for it and moves the horizon to its masked end.
+ * Not taken: --seedrepeat > 1, HSPsets without a horizon, match types other than DNA / protein / protein-vs-DNA: those
+ * sets keep the reference's own function.
+ * C4GPU_HSP_HOST=1 (CPU test of the seam): the extensions come from the reference's own HSPset_seed_hsp on scratch sets.
+ * C4GPU_HSP_CHECK=1: after the device call every extended seed is compared with that function's result (kept or dropped,
+ * ends, score, masked end); the run aborts at the first difference. */
 #include <string.h>
 #include <stdlib.h>
 
@@ -30,7 +35,7 @@ typedef struct { HSPset *set; GArray *seeds; /* guint pairs (query_start, target
 
 static GHashTable *hsp_pending = NULL;          /* HSPset* -> ShimSeedSet* */
 static GPtrArray *hsp_order = NULL;             /* ShimSeedSet*, in order of first seed */
-static struct { long sets, seeds, stored, flushes; double device_ms; } hst;
+static struct { long sets, seeds, stored, dropped, checked, flushes; double device_ms; } hst;
 
 static gint hsp_match_kind(HSPset *hsp_set){
     switch(hsp_set->param->match->type){
@@ -46,11 +51,6 @@ static gboolean hsp_eligible(HSPset *hsp_set){
     if(off < 0)
         off = shim_env("C4GPU_HSP_OFF") ? 1 : 0;
     if(off || (!hsp_set->horizon) || (hsp_set->param->seed_repeat > 1) || (hsp_match_kind(hsp_set) < 0))
-        return FALSE;
-    /* the mask functions are always set (match.c:670,679) and ask the sequence's alphabet: without --softmaskquery /
-     * --softmasktarget nothing is ever masked, the masked first extension (hspset.c:975-983) is then the plain one, and a
-     * second extension from its ends finds what the first one found */
-    if(hsp_set->query->alphabet->is_soft_masked || hsp_set->target->alphabet->is_soft_masked)
         return FALSE;
     if(shim_batch_size() <= 0)
         return FALSE;
@@ -91,8 +91,80 @@ void HSPset_seed_hsp(HSPset *hsp_set, guint query_start, guint target_start){
     return;
     }
 
-/* the replay of one set: hspset.c:936-958 (seed_repeat == 1) around the precomputed HSPs */
-static void hsp_replay(ShimSeedSet *ss, const c4gpu_hsp *hsp){
+/* The mask functions are always set (match.c:670,679) and ask the sequence's alphabet: without --softmaskquery /
+ * --softmasktarget nothing is ever masked, the masked first extension (hspset.c:981-990) is then the plain one, a second
+ * extension from its ends finds what the first one found, and the threshold can wait for HSP_store.  Only a set with a
+ * soft-masked alphabet needs the two stages. */
+static gboolean hsp_set_masked(HSPset *hsp_set){
+    return hsp_set->query->alphabet->is_soft_masked || hsp_set->target->alphabet->is_soft_masked;
+    }
+
+/* The reference's own answer for one seed, on a scratch HSPset (nothing in its way).  A plain set stores whatever grows
+ * (threshold -1: the replay applies the real one); a soft-masked set runs with its real threshold, because the masked stage
+ * compares with it: dropped = the scratch set stayed empty, and its horizon entry is the masked end (hspset.c:985-989),
+ * handed back as (target_start = that end, length = 0). */
+static void hsp_host_one(HSPset *hsp_set, guint query_start, guint target_start, c4gpu_hsp *out, gint32 *dropped){
+    register gboolean masked = hsp_set_masked(hsp_set);
+    register C4_Score keep = hsp_set->param->threshold;
+    register HSPset *one;
+    if(!masked)
+        hsp_set->param->threshold = -1;
+    one = HSPset_create(hsp_set->query, hsp_set->target, hsp_set->param);
+    HSPset_seed_hsp_cpu(one, query_start, target_start);
+    HSPset_finalise_cpu(one);
+    if(one->hsp_list->len){
+        register HSP *h = one->hsp_list->pdata[0];
+        out->query_start = h->query_start; out->target_start = h->target_start;
+        out->length = h->length; out->score = h->score; out->cobs = h->cobs;
+        *dropped = 0;
+    } else {
+        register gint aq = hsp_set->param->match->query->advance, at = hsp_set->param->match->target->advance;
+        register gint diag_pos = (target_start * aq) - (query_start * at);
+        register gint section_pos = (diag_pos + hsp_set->query->len) % hsp_set->query->len;
+        out->query_start = 0; out->length = 0; out->score = 0; out->cobs = 0;
+        out->target_start = (section_pos >= 0) ? one->horizon[0][section_pos][query_start % aq][target_start % at] : 0;
+        *dropped = 1;
+        }
+    HSPset_destroy(one);
+    hsp_set->param->threshold = keep;
+    return;
+    }
+
+/* C4GPU_HSP_CHECK: every seed the device extended against the reference's own function */
+static void hsp_check(ShimSeedSet *ss, const c4gpu_hsp *hsp, const gint32 *dropped){
+    register HSPset *hsp_set = ss->set;
+    register gint aq = hsp_set->param->match->query->advance, at = hsp_set->param->match->target->advance;
+    register guint k;
+    for(k = 0; k < ss->seeds->len; k++){
+        register guint *seed = &g_array_index(ss->seeds, guint, 2 * k);
+        register gint diag_pos = (seed[1] * aq) - (seed[0] * at);
+        register gint section_pos = (diag_pos + hsp_set->query->len) % hsp_set->query->len;
+        c4gpu_hsp ref;
+        gint32 ref_dropped;
+        register gboolean same;
+        if(hsp[k].length < 0)                                            /* skipped under its chain's horizon */
+            continue;
+        hsp_host_one(hsp_set, seed[0], seed[1], &ref, &ref_dropped);
+        if(ref_dropped != dropped[k])
+            same = FALSE;
+        else if(ref_dropped)
+            same = (section_pos < 0) || (ref.target_start == hsp[k].target_start + hsp[k].length * at);
+        else
+            same = (ref.query_start == hsp[k].query_start) && (ref.target_start == hsp[k].target_start)
+                && (ref.length == hsp[k].length) && (ref.score == hsp[k].score);
+        if(!same)
+            g_error("C4GPU_HSP_CHECK: seed (%u, %u) of [%s] vs [%s]: device %s (%d, %d, %d, score %d), reference %s (%d, %d, %d, score %d)",
+                    seed[0], seed[1], hsp_set->query->id, hsp_set->target->id,
+                    dropped[k] ? "dropped" : "kept", hsp[k].query_start, hsp[k].target_start, hsp[k].length, hsp[k].score,
+                    ref_dropped ? "dropped, masked end" : "kept", ref.query_start, ref.target_start, ref.length, ref.score);
+        hst.checked++;
+        }
+    return;
+    }
+
+/* the replay of one set: hspset.c:936-958 (seed_repeat == 1) around the precomputed HSPs; a dropped seed (soft-masked
+ * sets, hspset.c:985-989) stores nothing and moves the horizon to its masked end */
+static void hsp_replay(ShimSeedSet *ss, const c4gpu_hsp *hsp, const gint32 *dropped){
     register HSPset *hsp_set = ss->set;
     register gint aq = hsp_set->param->match->query->advance, at = hsp_set->param->match->target->advance;
     register guint k;
@@ -108,6 +180,12 @@ static void hsp_replay(ShimSeedSet *ss, const c4gpu_hsp *hsp){
         register gint *horizon = (section_pos >= 0) ? &hsp_set->horizon[0][section_pos][query_frame][target_frame] : NULL;
         if(horizon && ((gint)seed[1] < *horizon))
             continue;
+        if(dropped[k]){
+            if(horizon)
+                *horizon = hsp[k].target_start + hsp[k].length * at;     /* HSP_target_end of the masked-extended nascent HSP */
+            hst.dropped++;
+            continue;
+            }
         HSPset_add_known_hsp(hsp_set, hsp[k].query_start, hsp[k].target_start, hsp[k].length);
         if(horizon)
             *horizon = hsp[k].target_start + hsp[k].length * at;         /* HSP_target_end */
@@ -124,7 +202,7 @@ static void hsp_flush(void){
     c4gpu_hsp_seed *seeds;
     c4gpu_hsp *hsps;
     gint *set_pair, *set_first;
-    gint32 *chain_of = NULL, *horizon0 = NULL, *gc = NULL;
+    gint32 *chain_of = NULL, *horizon0 = NULL, *gc = NULL, *dropped;
     gint n_chains = 0;
     gboolean ok = TRUE;
     gint64 t0 = g_get_monotonic_time();
@@ -135,6 +213,7 @@ static void hsp_flush(void){
     pairs = g_new0(c4gpu_pair, n_sets);
     seeds = g_new(c4gpu_hsp_seed, total + 1);
     hsps = g_new0(c4gpu_hsp, total + 1);
+    dropped = g_new0(gint32, total + 1);
     set_pair = g_new(gint, n_sets);
     set_first = g_new(gint, n_sets + 1);
     seq_index = g_hash_table_new(g_direct_hash, g_direct_equal);
@@ -204,25 +283,21 @@ static void hsp_flush(void){
         horizon0 = (gint32*)g_array_free(h0, FALSE);
         }
     if(shim_env("C4GPU_HSP_HOST")){
-        /* the reference's own extension, one scratch HSPset per seed (nothing in its way) */
+        /* the reference's own extension, one scratch HSPset per seed (hsp_host_one) */
         for(i = 0; i < n_sets; i++){
             register ShimSeedSet *ss = hsp_order->pdata[i];
-            register C4_Score keep = ss->set->param->threshold;
-            ss->set->param->threshold = -1;                  /* store whatever grows: the replay applies the threshold */
-            for(k = 0; k < ss->seeds->len; k++){
-                register HSPset *one = HSPset_create(ss->set->query, ss->set->target, ss->set->param);
-                register HSP *h;
-                HSPset_seed_hsp_cpu(one, seeds[set_first[i] + k].query_start, seeds[set_first[i] + k].target_start);
-                HSPset_finalise_cpu(one);
-                h = one->hsp_list->pdata[0];
-                hsps[set_first[i] + k].query_start = h->query_start; hsps[set_first[i] + k].target_start = h->target_start;
-                hsps[set_first[i] + k].length = h->length; hsps[set_first[i] + k].score = h->score;
-                HSPset_destroy(one);
-                }
-            ss->set->param->threshold = keep;
+            for(k = 0; k < ss->seeds->len; k++)
+                hsp_host_one(ss->set, seeds[set_first[i] + k].query_start, seeds[set_first[i] + k].target_start,
+                             hsps + set_first[i] + k, dropped + set_first[i] + k);
             }
     } else {
-        /* one launch per (match type, seed length, dropoff): in practice one or two per scan */
+        /* one launch per (match type, seed length, dropoff, threshold, the two mask flags): in practice one or two per scan */
+#define HSP_SAME_GROUP(a, b) ((hsp_match_kind((a)->set) == hsp_match_kind((b)->set)) \
+                           && ((a)->set->param->seedlen == (b)->set->param->seedlen) \
+                           && ((a)->set->param->dropoff == (b)->set->param->dropoff) \
+                           && ((a)->set->param->threshold == (b)->set->param->threshold) \
+                           && ((a)->set->query->alphabet->is_soft_masked == (b)->set->query->alphabet->is_soft_masked) \
+                           && ((a)->set->target->alphabet->is_soft_masked == (b)->set->target->alphabet->is_soft_masked))
         gboolean *done = g_new0(gboolean, n_sets);
         c4gpu_params params;
         shim_hsp_params(&params);
@@ -231,15 +306,17 @@ static void hsp_flush(void){
             register gint kind = hsp_match_kind(si->set), first = -1, count = 0;
             c4gpu_hsp_seed *gs;
             c4gpu_hsp *go;
+            gint32 *gd;
+            register gint mq = si->set->query->alphabet->is_soft_masked ? 1 : 0, mt = si->set->target->alphabet->is_soft_masked ? 1 : 0;
             if(done[i])
                 continue;
             gs = g_new(c4gpu_hsp_seed, total + 1);
             go = g_new(c4gpu_hsp, total + 1);
+            gd = g_new0(gint32, total + 1);
             gc = chain_of ? g_new(gint32, total + 1) : NULL;
             for(k = i; k < n_sets; k++){
                 register ShimSeedSet *sk = hsp_order->pdata[k];
-                if(done[k] || (hsp_match_kind(sk->set) != kind) || (sk->set->param->seedlen != si->set->param->seedlen)
-                || (sk->set->param->dropoff != si->set->param->dropoff))
+                if(done[k] || !HSP_SAME_GROUP(sk, si))
                     continue;
                 done[k] = TRUE;
                 memcpy(gs + count, seeds + set_first[k], sizeof(c4gpu_hsp_seed) * (set_first[k+1] - set_first[k]));
@@ -248,7 +325,15 @@ static void hsp_flush(void){
                 count += set_first[k+1] - set_first[k];
                 (void)first;
                 }
-            if(gc){
+            if(mq || mt){                                   /* the two-stage rule; runs without soft-masking keep the old calls */
+                if((gc ? c4gpu_hsp_extend_chains_masked(shim_get_ctx(), &params, kind, pairs, n_sets, si->set->param->seedlen,
+                                                        si->set->param->dropoff, mq, mt, si->set->param->threshold, gs, count,
+                                                        gc, n_chains, horizon0, go, gd)
+                       : c4gpu_hsp_extend_batch_masked(shim_get_ctx(), &params, kind, pairs, n_sets, si->set->param->seedlen,
+                                                       si->set->param->dropoff, mq, mt, si->set->param->threshold, gs, count,
+                                                       go, gd)) != 0)
+                    ok = FALSE;
+            } else if(gc){
                 if(c4gpu_hsp_extend_chains(shim_get_ctx(), &params, kind, pairs, n_sets, si->set->param->seedlen,
                                            si->set->param->dropoff, gs, count, gc, n_chains, horizon0, go) != 0)
                     ok = FALSE;
@@ -257,20 +342,24 @@ static void hsp_flush(void){
                 ok = FALSE;
             for(k = i, count = 0; ok && (k < n_sets); k++){            /* scatter back in the same order */
                 register ShimSeedSet *sk = hsp_order->pdata[k];
-                if((hsp_match_kind(sk->set) != kind) || (sk->set->param->seedlen != si->set->param->seedlen)
-                || (sk->set->param->dropoff != si->set->param->dropoff) || (k < i))
+                if(!HSP_SAME_GROUP(sk, si))
                     continue;
                 memcpy(hsps + set_first[k], go + count, sizeof(c4gpu_hsp) * (set_first[k+1] - set_first[k]));
+                memcpy(dropped + set_first[k], gd + count, sizeof(gint32) * (set_first[k+1] - set_first[k]));
                 count += set_first[k+1] - set_first[k];
                 }
-            g_free(gs); g_free(go); g_free(gc);
+            g_free(gs); g_free(go); g_free(gc); g_free(gd);
             }
+#undef HSP_SAME_GROUP
         g_free(done);
+        if(ok && shim_env("C4GPU_HSP_CHECK"))
+            for(i = 0; i < n_sets; i++)
+                hsp_check(hsp_order->pdata[i], hsps + set_first[i], dropped + set_first[i]);
         }
     for(i = 0; i < n_sets; i++){
         register ShimSeedSet *ss = hsp_order->pdata[i];
         if(ok){
-            hsp_replay(ss, hsps + set_first[i]);
+            hsp_replay(ss, hsps + set_first[i], dropped + set_first[i]);
         } else {                                             /* the device refused (e.g. a residue outside the alphabet) */
             ss->set->is_empty = TRUE;
             for(k = 0; k < ss->seeds->len; k++)
@@ -288,7 +377,7 @@ static void hsp_flush(void){
         g_free(strs->pdata[i]);
     g_ptr_array_free(strs, TRUE);
     g_hash_table_destroy(seq_index);
-    g_free(pairs); g_free(seeds); g_free(hsps); g_free(set_pair); g_free(set_first); g_free(chain_of); g_free(horizon0);
+    g_free(pairs); g_free(seeds); g_free(hsps); g_free(dropped); g_free(set_pair); g_free(set_first); g_free(chain_of); g_free(horizon0);
     hst.flushes++;
     hst.device_ms += (g_get_monotonic_time() - t0) / 1e3;
     return;
@@ -303,6 +392,7 @@ HSPset *HSPset_finalise(HSPset *hsp_set){
 void shim_hsp_report(void){
     if(shim_env("C4GPU_VERBOSE") && hst.sets)
         g_message("c4gpu hsp: %ld word hits of %ld HSP sets extended in %ld device batch(es) (%.0f ms incl. flattening and "
-                  "replay), %ld HSPs passed their horizon", hst.seeds, hst.sets, hst.flushes, hst.device_ms, hst.stored);
+                  "replay), %ld HSPs passed their horizon, %ld seeds dropped at masked ends, %ld checked against the reference",
+                  hst.seeds, hst.sets, hst.flushes, hst.device_ms, hst.stored, hst.dropped, hst.checked);
     return;
     }

@@ -378,6 +378,175 @@ def run_ner_cli(name):
     print(name, len(out["pairs"]), "pairs,", sum(len(p["stdout"]) for p in out["pairs"]), "lines")
 
 
+# ---- soft-masked HSP seeding (hspset.c:981-995): the reference BINARY with and without --softmaskquery / --softmasktarget ----
+# refdump --cmd hsp builds its sequences on a non-masked alphabet, so these sets record exonerate -m ungapped --showsugar yes:
+# GAM_Result_ungapped_create reports every kept HSP as one alignment, so every sugar line is an HSP (start, end, score).
+# --score 1 lets every stored HSP through the report threshold (the HSP threshold alone decides); --proteinwordlimit 0 keeps
+# the protein word neighbourhood to the words themselves, so that "every shared word" is what the seeder reports.
+SOFTMASK_SETS = {      # name -> (match, mask query, mask target)
+    "hsp_softmask_dna2dna_t": ("dna2dna", False, True), "hsp_softmask_dna2dna_q": ("dna2dna", True, False),
+    "hsp_softmask_dna2dna_qt": ("dna2dna", True, True),
+    "hsp_softmask_protein2protein_t": ("protein2protein", False, True), "hsp_softmask_protein2protein_q": ("protein2protein", True, False),
+    "hsp_softmask_protein2dna_t": ("protein2dna", False, True), "hsp_softmask_protein2dna_qt": ("protein2dna", True, True),
+}
+SOFTMASK_HSP = {"dna2dna": dict(seedlen=12, dropoff=30, threshold=75, target_advance=1),
+                "protein2protein": dict(seedlen=6, dropoff=20, threshold=30, target_advance=1),
+                "protein2dna": dict(seedlen=6, dropoff=20, threshold=30, target_advance=3)}
+WEAK_AA = "AILVS"          # 4 each against themselves in blosum62: a six-residue word scores 24, under the threshold of 30
+
+
+def upper_only(s, spans):
+    """s in lower case except the [a, b) spans."""
+    out = s.lower()
+    for a, b in spans:
+        out = out[:a] + s[a:b].upper() + out[b:]
+    return out
+
+
+def softmask_cases(match, mq, mt, seed):
+    """Small pairs (queries <= 240 nt / 80 aa, targets <= 900 nt) around a copy of the query in the target that is lower case
+    on the masked side(s) except for islands: islands from one seed length up (the short ones are dropped: nothing else of
+    the copy seeds), a mask directly against both ends of the seed (the island of exactly one seed length), a mask at position
+    0 and at the last position of a sequence, two islands on one diagonal (the first dropped, the second kept), a side masked
+    throughout, and for the advance-3 target a single lower-case base as 1st, 2nd, 3rd base of the codon next to the seed."""
+    rng = random.Random(seed)
+    protein_q = match != "dna2dna"
+    w = SOFTMASK_HSP[match]["seedlen"]
+    cases = []
+
+    def query(n, weak=()):
+        q = list(rand_dna(rng, n, AA if protein_q else "ACGT"))
+        for a, b in weak:
+            for x in range(a, b):
+                q[x] = rng.choice([c for c in WEAK_AA if x == a or c != q[x - 1]])       # no runs: no repeated words
+        return "".join(q)
+
+    def pair(cid, q, spans, lead=None, trail=None, spans_t=None):
+        """The copy of q with the islands `spans` (query coordinates) upper case on the masked side(s)."""
+        body = q if match != "protein2dna" else "".join(rng.choice(CODON[a]) for a in q)
+        unit = 3 if match == "protein2dna" else 1
+        tspans = [(a * unit, b * unit) for a, b in (spans if spans_t is None else spans_t)]
+        lead = rand_dna(rng, rng.randint(0, 60)) if lead is None else lead
+        trail = rand_dna(rng, rng.randint(0, 60)) if trail is None else trail
+        if match == "protein2protein":
+            lead, trail = rand_dna(rng, len(lead) // 3, AA), rand_dna(rng, len(trail) // 3, AA)
+        t = lead + (upper_only(body, tspans) if mt else body) + trail
+        cases.append((cid, upper_only(q, spans) if mq else q, t))
+
+    lens = [w, w, w, w + 1, w + 1, w + 1, w + 2, w + 2, w + 3, w + 4, w + 6, w + 8, w + 12] if not protein_q else \
+           [w, w, w, w, w + 1, w + 1, w + 1, w + 1, w + 2, w + 3, w + 4, w + 6]
+    n = 80 if protein_q else 200
+    for k, L in enumerate(lens):
+        a = rng.randint(8, n - L - 8)
+        q = query(n, [(a, a + L)] if protein_q else ())
+        if mq and mt:               # the two sides' islands overlap on [a, a + L) only
+            pair("isl%02d_%d" % (k, L), q, [(max(0, a - 5), a + L)], spans_t=[(a, min(n, a + L + 4))])
+        else:
+            pair("isl%02d_%d" % (k, L), q, [(a, a + L)])
+    # a mask at position 0 and at the last position of the masked sequence(s): the copy is the whole target
+    for k in range(2):
+        q = query(n // 2)
+        pair("edge%d" % k, q, [(1, len(q) - 1)], lead="", trail="")
+    # two islands on one diagonal: the first dropped, the second kept; the dropped seed's horizon is its masked end
+    for k in range(3):
+        a = rng.randint(6, 20)
+        L1, gap, L2 = w + (k % 2), rng.randint(3, 9), w + 9 + k
+        q = query(n, [(a, a + L1)] if protein_q else ())
+        pair("two%d" % k, q, [(a, a + L1), (a + L1 + gap, a + L1 + gap + L2)])
+    # masked throughout: nothing seeds
+    q = query(n // 2)
+    pair("all0", q, [])
+    if match == "protein2dna" and mt:
+        # a weak seed (24) with a tryptophan (11) next to it, whose codon TGG has ONE lower-case base; everything beyond is lower
+        # case.  A codon is masked when any of its three bases is (match.c:212-220): the seed stays at 24 and is dropped;
+        # ignoring one of the bases would reach 35 and keep it.  (TGG with any one base unknown translates to X: no word of
+        # the masked target runs over it.)
+        for side in ("right", "left"):
+            for base in range(3):
+                a = 20
+                q = query(60, [(a, a + w)])
+                nb = a + w if side == "right" else a - 1
+                q = q[:nb] + "W" + q[nb + 1:]
+                body = "".join(rng.choice(CODON[x]) for x in q)
+                lo, hi = (a, a + w + 1) if side == "right" else (a - 1, a + w)
+                t = upper_only(body, [(3 * lo, 3 * hi)])
+                x = 3 * nb + base
+                t = t[:x] + t[x].lower() + t[x + 1:]
+                cases.append(("codon_%s%d" % (side, base), upper_only(q, [(lo, hi)]) if mq else q,
+                              rand_dna(rng, rng.randint(0, 30)) + t + rand_dna(rng, rng.randint(0, 30))))
+    if match == "dna2dna" and mt and not mq:
+        # the second stage is not a plain extension (hspset.c:992 starts from the first stage's score, and goes left after that
+        # stage has gone right).  --dnahspdropoff 100 in the set below is above the seed's own 60.  Left of a 16 nt island
+        # (80 in stage 1) lie m mismatches and then 40 masked matches; right of it 60 masked matches.
+        #   m = 17 (-68): a plain extension from the island's first word stops going left below zero (60 - 64 - 4); stage 2 goes
+        #           left from 80 and crosses: the HSP is the whole copy, as without the option
+        #   m = 21 (-84): stage 2 stops below zero as well (80 - 84): kept, but with another start and score than without
+        #           the option, where the words of the left part seed first and cross the other way
+        for m in (17, 21):
+            q = rand_dna(rng, 40 + m + 16 + 60)
+            other = {"A": "C", "C": "A", "G": "T", "T": "G"}
+            body = q[:40] + "".join(other[c] for c in q[40:40 + m]) + q[40 + m:]
+            t = rand_dna(rng, 25) + upper_only(body, [(40, 40 + m + 16)]) + rand_dna(rng, 30)
+            cases.append(("stage2_m%d" % m, q, t))
+    return cases
+
+
+def run_hsp_softmask(name):
+    match, mq, mt = SOFTMASK_SETS[name]
+    par = dict(SOFTMASK_HSP[match], match=match, mask_query=mq, mask_target=mt, seed_repeat=1)
+    types = {"dna2dna": ("dna", "dna"), "protein2protein": ("protein", "protein"), "protein2dna": ("protein", "dna")}[match]
+    flags = ["-m", "ungapped", "-Q", types[0], "-T", types[1], "--showsugar", "yes", "--showalignment", "no", "--showvulgar", "no",
+             "--score", "1", "-V", "0"]
+    if match != "dna2dna":
+        flags += ["--proteinwordlimit", "0"]
+    if name == "hsp_softmask_dna2dna_t":
+        flags += ["--dnahspdropoff", "100"]
+        par["dropoff"] = 100
+    soft = (["--softmaskquery", "yes"] if mq else []) + (["--softmasktarget", "yes"] if mt else [])
+    par["flags"], par["softmask_flags"] = flags, soft
+    cases = softmask_cases(match, mq, mt, 9100 + len(name) + 7 * mq)
+    recs = []
+    for cid, q, t in cases:
+        assert len(q) <= (240 if match == "dna2dna" else 80) and len(t) <= 900, (cid, len(q), len(t))
+        rec = {"id": cid, "query": q, "target": t}
+        for key, extra in (("plain", []), ("masked", soft)):
+            with tempfile.TemporaryDirectory() as d:
+                qf, tf = os.path.join(d, "q.fa"), os.path.join(d, "t.fa")
+                with open(qf, "w") as f:
+                    f.write(">%s\n%s\n" % (cid, q))
+                with open(tf, "w") as f:
+                    f.write(">tg_%s\n%s\n" % (cid, t))
+                r = subprocess.run([REF_EXONERATE] + flags + extra + [qf, tf], stdout=subprocess.PIPE, stderr=subprocess.PIPE, check=True)
+            hsps = []
+            for l in r.stdout.decode().split("\n"):
+                if not l.startswith("sugar:"):
+                    continue
+                s = l.split()                    # sugar: qid qstart qend qstrand tid tstart tend tstrand score
+                if s[4] == "-" or s[8] == "-":   # a chance hit on a reverse strand: not part of these records
+                    continue
+                hsps.append([int(s[2]), int(s[6]), int(s[3]) - int(s[2]), int(s[9])])
+                assert (int(s[7]) - int(s[6])) == hsps[-1][2] * par["target_advance"], l
+            rec[key] = sorted(hsps)
+        recs.append(rec)
+    # the mask must decide, from the reference's two outputs alone
+    lost = sum(len([h for h in r["plain"] if h not in r["masked"]]) for r in recs)
+    assert lost >= 6, (name, "the mask decides only", lost, "HSPs")
+    assert any(not r["masked"] and r["plain"] for r in recs), name
+    for r in recs:
+        if r["id"].startswith("stage2_m21"):     # kept, but not the HSP of the run without the option
+            assert r["masked"] and r["plain"] and r["masked"] != r["plain"], r
+        if r["id"].startswith("stage2_m17"):
+            assert r["masked"] and r["masked"] == r["plain"], r
+        if r["id"].startswith(("all", "codon_")):
+            assert not r["masked"] and r["plain"], r
+    with open(os.path.join(OUT, name + ".jsonl"), "w") as f:
+        f.write(json.dumps({"params": par}, separators=(",", ":")) + "\n")
+        for r in recs:
+            f.write(json.dumps(r, separators=(",", ":")) + "\n")
+    print(name, len(recs), "pairs,", sum(len(r["plain"]) for r in recs), "HSPs without the option,",
+          sum(len(r["masked"]) for r in recs), "with it,", lost, "lost to the mask")
+
+
 def run(model, cases, dpmemory, extra=()):
     # (a case may carry a fourth entry: the query's CDS annotation (cds_start, cds_length) -- exonerate's --annotation)
     with tempfile.NamedTemporaryFile("w", suffix=".tsv", delete=False) as f:
@@ -856,6 +1025,9 @@ def main():
     for name in sorted(NER_CLI_SETS):
         if (not only) or name in only:
             run_ner_cli(name)
+    for name in sorted(SOFTMASK_SETS):
+        if (not only) or name in only:
+            run_hsp_softmask(name)
     # the translated models (ungapped.c:106-166 with CODON2CODON, coding2coding.c:50-66): match advance 3/3.  refdump takes any
     # Model_Type name; these records pin the CPU oracle's 3:3 match as well (tests/test_oracle_codon.py)
     cr = random.Random(3303)
