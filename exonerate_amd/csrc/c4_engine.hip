@@ -26,6 +26,7 @@
 #include "c4_memrule.h"
 #include "c4_launch.h"
 #include "c4_kernel_choice.h"
+#include "c4_pk16_bias.h"
 #include "c4_sdp_launch.h"
 #include "c4_sdp_host.h"
 

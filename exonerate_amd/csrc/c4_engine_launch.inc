@@ -65,6 +65,18 @@ double splice_best_sum(const c4gpu_splice_model &sp, bool absolute) {
     return sum;
 }
 
+// ... and at its worst: the sum of the rows' smallest entries; a row without a negative entry adds nothing (the window of a
+// position near an end of the sequence is clipped: any run of rows can be missing)
+double splice_worst_sum(const c4gpu_splice_model &sp) {
+    double sum = 0;
+    for (int r = 0; r < sp.model_length && r < C4GPU_SPLICE_MAX_LEN; r++) {
+        double mn = 0;
+        for (int c = 0; c < 5; c++) mn = std::min(mn, (double)sp.data[r][c]);
+        sum += mn;
+    }
+    return sum;
+}
+
 struct Engine {
     c4gpu_ctx *ctx;
     const c4gpu_model *model;
@@ -76,6 +88,8 @@ struct Engine {
     // here, and parameters outside that range get the general kernels (all masks kept) instead.
     bool local_exact = true;
     bool pk16_params_ok = false;         // see init: the parameters allow the packed 16-bit score pass
+    // ... and its biased (staged) forms: no negative addend between PK16_ADDEND_MAX and "clamps to -32 768" (c4_pk16_bias.h)
+    bool pk16_bias_ok = false;
     // largest magnitude one transition can add (calc constants, substitution scores, a splice model's best column sum):
     // what the continuation kernels without the row-0 mask need to stay exact (cont_free_ok)
     double calc_bound = 0;
@@ -177,9 +191,10 @@ struct Engine {
             double mmax = 0;
             for (int i = 0; i < 24 * 24; i++) mmax = std::max(mmax, (double)kp.submat[i]);
             pk16_match_max = (int)std::max(1.0, mmax);
-            pk16_params_ok = pmax <= 16000.0 && smax <= 16000.0 && params->min_intron >= 0 && params->min_intron <= 30000 &&
+            pk16_params_ok = pmax <= (double)PK16_SCORE_MAX && smax <= (double)PK16_SCORE_MAX && params->min_intron >= 0 && params->min_intron <= 30000 &&
                              params->max_intron >= params->min_intron;
             pk16_max_intron = params->max_intron;
+            pk16_bias_ok = false;
             if (veto) {
                 // a match score of -987654321 is no "small calc": the kernels that keep every validity mask and the 32-bit
                 // passes serve such batches (what parameters of that magnitude get: *_hugegap sets)
@@ -209,6 +224,21 @@ struct Engine {
                     }
                     if (pre > -0x40000000LL && post > -0x40000000LL) gain = std::max(gain, pre + post);
                 }
+                // the biased forms: every site at its worst, rounded as the predictor rounds (one more for the float sums), with
+                // the calc constant of a pre-splice transition folded in as ss16_kernel / SpliceFold fold it (--forcegtag's
+                // -987 654 321 is written in a sum's place and clamps to exactly -32 768, which those forms carry)
+                long long site_worst[4] = {0, 0, 0, 0}, post_best = 0;
+                for (int i = 0; i < m->n_calcs; i++) {
+                    const c4gpu_calc &cc = m->calcs[i];
+                    const int prm = cc.param & 3;
+                    const long long worst = (long long)std::floor(splice_worst_sum(params->splice[prm]) - 0.5) - 1;
+                    if (cc.kind == C4GPU_CALC_SPLICE_PRE) site_worst[prm] = std::min(site_worst[prm], (long long)cc.value + worst);
+                    if (cc.kind == C4GPU_CALC_SPLICE_POST) {
+                        site_worst[prm] = std::min(site_worst[prm], worst);
+                        post_best = std::max<long long>(post_best, best[prm]);
+                    }
+                }
+                pk16_bias_ok = pk16_bias_fits(kp.submat, 24 * 24, kp.calc_value, m->n_calcs, site_worst, 4, post_best);
                 pk16_intron_gain = (int)std::max<long long>(0, std::min<long long>(gain, 1 << 20));
                 pk16_intron_cols = std::max(4, params->min_intron);
                 // KParams::loop_tr (c4_viterbi_kernel.h, viterbi_kernel): a state s with a loop (0, 1) that adds nothing, entered
@@ -283,7 +313,7 @@ struct Engine {
     bool pk16_fits(int query_length, int target_length) const {
         const double gain = (double)(query_length + 1) * pk16_match_max +
                             (double)(target_length / pk16_intron_cols + 1) * pk16_intron_gain;
-        return gain <= 16000.0 && (!family_has_splice(family) || (long long)target_length + 4 <= (long long)pk16_max_intron);
+        return gain <= (double)PK16_SCORE_MAX && (!family_has_splice(family) || (long long)target_length + 4 <= (long long)pk16_max_intron);
     }
     // the four splice values of every target position as the packed passes add them (ss16_kernel): built once per batch,
     // finished before the lock is released (the other lane launches on another stream)
@@ -391,6 +421,7 @@ struct Engine {
         }
         if (seed) { f.seed_mode = seed->mode; f.kshift = seed->kshift; f.fmt16 = seed->fmt16; }
         f.pk16_params_ok = pk16_params_ok;
+        f.pk16_bias_unfit = !pk16_bias_ok;
         f.pk16_all_fit = f.seed_mode == 1;
         for (int i = 0; i < n && f.pk16_all_fit; i++) f.pk16_all_fit = pk16_fits(specs[i].region.query_length, specs[i].region.target_length);
         f.tdense_n = seqs.tdense_n; f.ss16_built = seqs.ss16_built;

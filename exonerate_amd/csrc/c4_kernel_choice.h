@@ -106,6 +106,7 @@ struct LaunchFacts {
     int cu_count = 0;
     const int *query_length = nullptr; // of the jobs of a launch without continuation (the others are not chosen by size)
     int n_lengths = 0;
+    bool pk16_bias_unfit = false;      // !Engine::pk16_bias_ok: an addend the biased (staged) forms of the packed score pass cannot carry
 };
 
 struct KernelChoice {
@@ -149,6 +150,9 @@ inline void choose_pk16(const LaunchFacts &f, const Switches &sw, KernelChoice &
     for (int i = 0; i < f.n_lengths; i++) rows = std::max(rows, f.query_length[i] + 1);
     if (rows > 32000) return;
     c.ki = kd; c.fmt16 = true;
+    // the staged forms carry their scores biased (c4_viterbi16_kernel.h, BIAS): parameters with an addend that form cannot carry
+    // stay on the form that loads per step, with integer maxima
+    if (f.pk16_bias_unfit) return;
     // ... and with its column loop fed from LDS alone (staged) where every query fits the strips of one workgroup and the
     // targets hold few enough residue codes for the query profile
     const KernelInfo *ke = sw.pk16_io ? get_kernel_pk16(f.family, sw.pk16_io == 2 ? PK16_STAGED : PK16_STAGED_BARRIER) : nullptr;

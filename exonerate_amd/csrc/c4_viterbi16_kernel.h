@@ -22,9 +22,29 @@
 //   * the column dumps the region windows start from are written in the 32-bit kernel's own format (scores sign-extended,
 //     shadow = column - length - 2): a window computes from them what it computes from the 32-bit pass's dumps wherever a
 //     result can see it, and the host checks every window's corner score against this pass's score as before.
+//   * BIAS (every staged form): the score halves hold real + PK16_BIAS, so that a state without a payload and with three or more
+//     incoming transitions (the match states) takes its candidates through v_pk_maximum3_f16, two of them per instruction: for
+//     bit patterns in [0x0400, 0x7BFF], non-negative normal halves, the IEEE order is the integer order.  The rule: no NaN or
+//     infinity pattern -- as int16 [-1024, -1] and [31744, 32767] -- ever enters such a maximum in a cell a result reads.
+//       - legitimate values (cells with a real predecessor inside the rectangle): a match state is >= PK16_BIAS (START); a gap or
+//         intron state always has a candidate that is a match state plus ONE addend, so it is at least one negative addend below
+//         PK16_BIAS, and a candidate into a match state at most two: >= PK16_BIAS - 2 A >= 0x0400 (A: the largest magnitude of a
+//         negative addend, Engine::pk16_bias_ok); and no candidate exceeds its state, <= PK16_BIAS + 16 000 <= 0x7BFF (pk16_fits);
+//       - the lineage of `unset` (-32 768 plus what a path can gain) lies in [-32768, -32768 + 16 000 + a site]: negative finite
+//         halves, which lose to every legitimate operand under either order, and a match state always has START's PK16_BIAS among
+//         its operands: the (reversed) float order among negative halves never decides a value a result reads;
+//       - an addend of exactly -32 768 (a dead row's match score, a too-short intron, --forcegtag's sentinel clamped) takes a
+//         legitimate value to <= 0x7BFF - 32768 = -1 025 = 0xFBFF, a negative finite half; a later post-splice site adds at most
+//         PK16_POST_GAIN_MAX, which PK16_BIAS leaves room for; addends between are what the host's guard refuses;
+//       - cells of the shorter job of a lane beyond its own T may exceed 16 000 where an intron can gain, and then hold a NaN:
+//         the halves of a packed instruction are independent, such cells are neither dumped nor reported (j <= T[H] in both
+//         places), and every transition advances away from the rectangle, so nothing of them comes back.  (Their half then sends
+//         the wave through the end-cell bookkeeping, as a saturated 32 767 does in the integer form.)
+//     Adds stay signed and saturating, `unset` stays -32 768, the dumps hold real values (PK16_BIAS subtracted, saturating).
 // The two jobs of a lane need not have the same size: cells outside a job's own rectangle hold garbage that only flows
 // away from the rectangle (every transition advances), its loads are clamped, its end cells are ignored.
 #pragma once
+#include "c4_pk16_bias.h"
 #include "c4_viterbi_kernel.h"
 
 namespace c4k {
@@ -43,6 +63,13 @@ template <int VAR> __device__ __forceinline__ int pk_add(int a, int b) {
 template <int VAR> __device__ __forceinline__ int pk_max(int a, int b) {
     if constexpr (VAR >= 1) return __builtin_bit_cast(int, __builtin_elementwise_max(__builtin_bit_cast(pk_s2, a), __builtin_bit_cast(pk_s2, b)));
     else { int r; asm("v_pk_max_i16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+}
+// BIAS: the three-way maximum of non-negative finite halves as v_pk_maximum3_f16 (IEEE maximum, not maxnum: nothing is
+// canonicalised in between, and the nested form is fused into the one instruction)
+typedef _Float16 pk_h2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ int pk_max3(int a, int b, int c) {
+    return __builtin_bit_cast(int, __builtin_elementwise_maximum(__builtin_elementwise_maximum(__builtin_bit_cast(pk_h2, a), __builtin_bit_cast(pk_h2, b)),
+                                                                 __builtin_bit_cast(pk_h2, c)));
 }
 __device__ __forceinline__ int pk_sub(int a, int b) { int r; asm("v_pk_sub_i16 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "v"(b)); return r; }
 // per half: 0xffff where the half is negative, else 0
@@ -100,14 +127,28 @@ struct Dump16 {
 //     (job, code, lane) -- a query profile, rebuilt per strip: a step reads two entries (conflict-free: the bank depends on
 //     the lane only) instead of 2 R table words at computed addresses.
 // 301 -> ~225 instructions per step of 8 cells (profiles/r04_score_budget.md).
-template <class M, int R, int VAR = 0, bool DUMP16 = false, int IO = 0, int NCODE_ = 6, bool MEMC = false>
+template <class M, int R, int VAR = 0, bool DUMP16 = false, int IO = 0, int NCODE_ = 6, bool MEMC = false, bool BIAS = false>
 struct WaveDP16 {
     using F = Facts<M>;
+    static_assert(!BIAS || (IO == 1 && DUMP16), "the biased form is the staged one: dead rows by the profile, 16-bit dumps");
+    static constexpr int B_PK = BIAS ? PK16_BIAS * 0x10001 : 0;          // what START contributes, in both halves
     static_assert(M::MAXAQ == 1, "the packed forms exchange exactly one query row per step");
     using W32 = WaveDP<M, R, MODE_SCORE, false, true, false, false, 0, 1>;     // the 32-bit score pass: dump layout
     using D16 = Dump16<M>;
     static constexpr int NS = M::NS, NCOL = M::MAXAT + 1, W = 64 * R, DC = M::MAXAT, SEEDW = DUMP16 ? D16::SEEDW16 : W32::SEEDW;
     static constexpr bool live(int s) { return M::NDES > 0 && W32::slot_live(s, 0); }
+    // BIAS: a state whose candidates are reduced two per instruction (pk_max3): no payload to select, three or more of them
+    static constexpr int n_into(int s) { int n = 0; for (int k = 0; k < M::NT; k++) n += (M::tr[k].out == s); return n; }
+    static constexpr bool max3_state(int s) { return BIAS && s != M::END && !live(s) && n_into(s) >= 3; }
+    // BIAS: nothing reads END (Dump16); the end-cell test and bookkeeping take it from the states that enter it
+    static constexpr bool feeds_end(int s) { for (int k = 0; k < M::NT; k++) if (M::tr[k].out == M::END && M::tr[k].in == s) return true; return false; }
+    static_assert(!BIAS || !feeds_end(M::START), "END's value is the maximum of inner states");
+    // ... of the SAME cell, with nothing added: every transition into END stays in the cell and has no calc
+    static constexpr bool end_is_plain_max() {
+        for (int k = 0; k < M::NT; k++) if (M::tr[k].out == M::END && (M::tr[k].aq != 0 || M::tr[k].at != 0 || M::tr[k].calc >= 0)) return false;
+        return true;
+    }
+    static_assert(!BIAS || end_is_plain_max(), "the biased form takes END as the plain maximum of the states that enter it");
     static constexpr int NEXP = F::n_exported();
     static constexpr int n_exported_live() { int n = 0; for (int x = 0; x < NS; x++) n += (F::exported(x) && live(x)); return n; }
     // ints per column between strips: score pair + length pair per exported state (IO 1: a length pair only where one is live)
@@ -262,7 +303,9 @@ struct WaveDP16 {
     // them, nothing of them is dumped or reported) score DEAD_ROW against everything: their match state then never leaves the 0
     // START gives it, and their END never beats a best score -- without that the lanes that hold such rows would send their
     // wave through the end-cell bookkeeping in every step (counters of round 4: 131 instructions, a quarter of the waves).
-    static constexpr int DEAD_ROW = -16000;
+    // BIAS: -32 768 -- -16 000 plus a low legitimate value would land in the NaN band; -32 768 plus ANY legitimate value is
+    // <= -1 025, finite and below everything
+    static constexpr int DEAD_ROW = BIAS ? -32768 : -16000;
     __device__ __forceinline__ void build_profile(int i0) {
         static_for<2>([&](auto H_) __attribute__((always_inline)) { constexpr int H = H_;
             int qr[R];
@@ -306,12 +349,14 @@ struct WaveDP16 {
     template <int RR, int PH, bool JINT>
     __device__ __forceinline__ void eval_cell(int j, int ms, const int (&sp)[4]) {
         C16 &c = col[PH][RR];
+        int pend[NS];                                        // BIAS: the candidate of a max3_state waiting for a partner
         static_for<M::NT>([&](auto K_) __attribute__((always_inline)) { constexpr int K = K_;
             constexpr TrDesc t = M::tr[K];
+            if constexpr (BIAS && t.out == M::END) return;
             constexpr int PD = (PH - t.at + NCOL) % NCOL;
             const C16 &src = (t.aq == 0) ? col[PD][RR] : (RR > 0 ? col[PD][RR > 0 ? RR - 1 : 0] : nbr[PD]);
             int cand;
-            if constexpr (t.in == M::START) cand = 0;
+            if constexpr (t.in == M::START) cand = B_PK;
             else cand = src.sc[t.in];
             if constexpr (t.calc >= 0) {
                 constexpr CalcDesc cd = M::calc[t.calc];
@@ -338,6 +383,13 @@ struct WaveDP16 {
             if constexpr (F::code(K) == 1) {                     // the first transition into this state
                 c.sc[t.out] = cand;
                 if constexpr (live(t.out)) c.il[t.out] = ilc;
+            } else if constexpr (max3_state(t.out)) {
+                // the second, fourth ... candidate waits for the next one (a maximum: the order does not matter, see the header);
+                // nothing reads the state inside the cell before its last transition
+                constexpr int nth = F::code(K) - 1;
+                if constexpr (nth % 2 == 0) c.sc[t.out] = pk_max3(c.sc[t.out], pend[t.out], cand);
+                else if constexpr (nth + 1 < n_into(t.out)) pend[t.out] = cand;
+                else c.sc[t.out] = pk_max<VAR>(c.sc[t.out], cand);
             } else {
                 if constexpr (live(t.out)) {
                     const int win = pk_lt_mask<VAR>(c.sc[t.out], cand, fifteen);          // strict <: the newcomer wins
@@ -395,15 +447,31 @@ struct WaveDP16 {
         });
         // end cell (viterbi.c:778-791): a new maximum is rare; one packed maximum over the lane's cells decides
         {
-            int m = col[PH][0].sc[M::END];
-            static_for<R>([&](auto RR_) __attribute__((always_inline)) { constexpr int RR = RR_; if constexpr (RR > 0) m = pk_max<VAR>(m, col[PH][RR].sc[M::END]); });
+            int m = 0;
+            if constexpr (BIAS) {
+                // END of the lane's rows: the maximum of the states that enter it, two per instruction
+                int pend = 0, n = 0;
+                static_for<R>([&](auto RR_) __attribute__((always_inline)) { constexpr int RR = RR_;
+                    static_for<NS>([&](auto S_) __attribute__((always_inline)) { constexpr int S = S_;
+                        if constexpr (feeds_end(S)) {
+                            const int v = col[PH][RR].sc[S];
+                            if (n == 0) m = v;
+                            else if (n % 2 == 1) pend = v;
+                            else m = pk_max3(m, pend, v);
+                            n++;
+                        }
+                    });
+                });
+                if (n % 2 == 0) m = pk_max<VAR>(m, pend);
+            } else {
+                m = col[PH][0].sc[M::END];
+                static_for<R>([&](auto RR_) __attribute__((always_inline)) { constexpr int RR = RR_; if constexpr (RR > 0) m = pk_max<VAR>(m, col[PH][RR].sc[M::END]); });
+            }
             const bool cand = (pk_sub(best_pk, m) & NEG16) != 0;
             if (__builtin_amdgcn_ballot_w64(cand)) {
                 static_for<2>([&](auto H_) __attribute__((always_inline)) { constexpr int H = H_;
                     const bool jact = (j >= 0) & (j <= T[H]);
                     static_for<R>([&](auto RR_) __attribute__((always_inline)) { constexpr int RR = RR_;
-                        const int tsc = pk_half(col[PH][RR].sc[M::END], H);
-                        const bool upd = jact & (i0 + RR <= Q[H]) & (!best_set[H] | (best[H] < tsc));
                         // which transition into END holds it: the first assigns, later ones replace on strict < (viterbi.c:766-775)
                         int from = -1, fsc = 0;
                         static_for<M::NT>([&](auto K_) __attribute__((always_inline)) { constexpr int K = K_;
@@ -415,13 +483,17 @@ struct WaveDP16 {
                                 from = win ? t.in : from;
                             }
                         });
+                        // BIAS: END is not carried: it is what the winner holds, as a real score
+                        const int tsc = BIAS ? fsc - PK16_BIAS : pk_half(col[PH][RR].sc[M::END], H);
+                        const bool upd = jact & (i0 + RR <= Q[H]) & (!best_set[H] | (best[H] < tsc));
                         best[H] = upd ? tsc : best[H];
                         best_i[H] = upd ? (((i0 + RR) << 4) | from) : best_i[H];
                         best_j[H] = upd ? j : best_j[H];
                         best_set[H] = best_set[H] | upd;
                     });
                 });
-                best_pk = pk_pack(best_set[0] ? best[0] : pk_half(unset_pk, 0), best_set[1] ? best[1] : pk_half(unset_pk, 1));
+                constexpr int B = BIAS ? PK16_BIAS : 0;       // best_pk is compared with the cells: biased as they are
+                best_pk = pk_pack(best_set[0] ? best[0] + B : pk_half(unset_pk, 0), best_set[1] ? best[1] + B : pk_half(unset_pk, 1));
             }
         }
         for_exported([&](auto S_, int) __attribute__((always_inline)) { constexpr int S = S_;
@@ -477,7 +549,11 @@ struct WaveDP16 {
                                 auto half_reg = [&](auto HI_) __attribute__((always_inline)) -> int { constexpr int HI = HI_;
                                     constexpr int S = D16::state_of_half(HI);
                                     if constexpr (S < 0) return 0;
-                                    else if constexpr (HI < D16::n_inner()) return col[PH][RR].sc[S];
+                                    else if constexpr (HI < D16::n_inner()) {
+                                        // real values: a window computes from them what it computes from the integer form's dumps
+                                        if constexpr (BIAS) return pk_sub(col[PH][RR].sc[S], B_PK);
+                                        else return col[PH][RR].sc[S];
+                                    }
                                     else return pk_add<VAR>(col[PH][RR].il[S], lim_pk);
                                 };
                                 static_for<D16::SEEDW16>([&](auto K_) __attribute__((always_inline)) { constexpr int K = K_;
@@ -706,11 +782,11 @@ __global__ void ss16_kernel(const KParams *kp, const int *ss, long long ss_strid
 // launch holds an odd number: its high half repeats it)
 // (IO 1: `tdense` is the launch's residue-code table -- [0, 24) code -> dense index, [24, 24 + NCODE) dense index -> code; the
 // host takes this kernel only when every query fits NW strips and the targets hold at most NCODE codes)
-template <class M, int R, int NW, int WPE, int VAR = 0, bool DUMP16 = false, int IO = 0, int NCODE_ = 6, bool MEMC = false>
+template <class M, int R, int NW, int WPE, int VAR = 0, bool DUMP16 = false, int IO = 0, int NCODE_ = 6, bool MEMC = false, bool BIAS = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE, 8)))
 void viterbi16_kernel_mw(const KParams *kparams, DevSeqs seqs, const DevJob *jobs, int n_jobs, DevResult *results,
                          DevScratch scratch, int *queue, const uint8_t *tdense = nullptr) {
-    using DP = WaveDP16<M, R, VAR, DUMP16, IO, NCODE_, MEMC>;
+    using DP = WaveDP16<M, R, VAR, DUMP16, IO, NCODE_, MEMC, BIAS>;
     // IO 1 leaves the launch constants in memory (a strip reads them once) and spends the LDS on the column stages (4 KB per
     // wave, 4 KB-aligned: the running stage address wraps with one v_and_or), the query profiles and the rings: 52.2 KB per
     // workgroup, three workgroups per CU

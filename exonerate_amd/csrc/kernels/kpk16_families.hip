@@ -7,10 +7,11 @@
 namespace c4k {
 // one form of the pass: the launcher, the occupancy handle and the sizes the host lays its buffers out by all follow from ONE
 // template argument list (IO 1, the staged forms: the launch's residue-code table arrives in LaunchArgs::aux)
+// (every staged form carries its scores biased, BIAS: the match states' maxima two candidates per instruction)
 template <class M, int R, int NW, int WPE, int VAR, bool D16, int IO = 0, int NCODE = 6, bool MEMC = false>
 struct Pk16 {
-    using DP = WaveDP16<M, R, VAR, D16, IO, NCODE, MEMC>;
-    static constexpr auto kernel = viterbi16_kernel_mw<M, R, NW, WPE, VAR, D16, IO, NCODE, MEMC>;
+    using DP = WaveDP16<M, R, VAR, D16, IO, NCODE, MEMC, IO == 1>;
+    static constexpr auto kernel = viterbi16_kernel_mw<M, R, NW, WPE, VAR, D16, IO, NCODE, MEMC, IO == 1>;
     static hipError_t launch(const LaunchArgs &a) {
         hipLaunchKernelGGL(kernel, dim3(a.grid), dim3(64 * NW), 0, a.stream, a.kp, a.seqs, a.jobs, a.n_jobs, a.results, a.scratch,
                            a.queue, IO ? reinterpret_cast<const uint8_t *>(a.aux) : nullptr);
