@@ -61,19 +61,23 @@ int model_family(const c4gpu_model &m) {
     if (model_matches<NerDesc>(m)) return FAM_NER;
     if (model_matches<UngappedCodonDesc>(m)) return FAM_UNGAPPED_CODON;
     if (model_matches<Coding2CodingDesc>(m)) return FAM_CODING2CODING;
+    if (model_matches<Coding2CodingStartDesc>(m)) return FAM_CODING2CODING_START;
+    if (model_matches<Coding2CodingEndDesc>(m)) return FAM_CODING2CODING_END;
+    if (model_matches<Coding2CodingJoinDesc>(m)) return FAM_CODING2CODING_JOIN;
     return -1;
 }
 
 static bool family_is_p2g_span(int fam) {
     return fam >= FAM_PROTEIN2GENOME_PHASE0_SPAN_SRC && fam <= FAM_PROTEIN2GENOME_PHASE2_SPAN_DST;
 }
+// both sequences translated (Match_3_3): the query array holds codon row codes too.  The derived models of coding2coding
+// included: an engine of theirs on a coding2coding batch reads the batch's translated query codes (c4gpu_batch_viterbi_model)
+bool family_is_codon(int fam) { return fam == FAM_UNGAPPED_CODON || (fam >= FAM_CODING2CODING && fam <= FAM_CODING2CODING_JOIN); }
 bool family_is_p2d(int fam) {
     return fam == FAM_UNGAPPED_P2D || fam == FAM_PROTEIN2DNA || fam == FAM_PROTEIN2GENOME ||
            (fam >= FAM_PROTEIN2DNA_START && fam <= FAM_PROTEIN2GENOME_JOIN) || family_is_p2g_span(fam) ||
-           fam == FAM_UNGAPPED_CODON || fam == FAM_CODING2CODING;
+           family_is_codon(fam);
 }
-// both sequences translated (Match_3_3): the query array holds codon row codes too
-bool family_is_codon(int fam) { return fam == FAM_UNGAPPED_CODON || fam == FAM_CODING2CODING; }
 bool family_has_splice(int fam) {
     return fam == FAM_EST2GENOME || fam == FAM_PROTEIN2GENOME || (fam >= FAM_EST2GENOME_FWD_START && fam <= FAM_EST2GENOME_REV_JOIN) ||
            (fam >= FAM_PROTEIN2GENOME_START && fam <= FAM_PROTEIN2GENOME_JOIN) ||

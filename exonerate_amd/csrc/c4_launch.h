@@ -25,6 +25,9 @@ enum Family { FAM_UNGAPPED = 0, FAM_AFFINE, FAM_EST2GENOME, FAM_UNGAPPED_P2D, FA
               // the translated DNA / DNA models, whose match advances 3/3 (max_query_advance = 3: the kernels hand three query
               // rows from lane to lane): ungapped:trans (ungapped.c:106-166) and coding2coding (coding2coding.c:50-66)
               FAM_UNGAPPED_CODON, FAM_CODING2CODING,
+              // BSDP's derived models of coding2coding (match state 2): transitions leave START with a query advance of 1, 2
+              // and 3; one-wave kernels with three rows per lane (R >= MAXAQ)
+              FAM_CODING2CODING_START, FAM_CODING2CODING_END, FAM_CODING2CODING_JOIN,
               FAM_COUNT };
 
 struct LaunchArgs {

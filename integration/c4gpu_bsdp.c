@@ -837,15 +837,58 @@ void shim_bsdp_flush(void){
     return;
     }
 
+/* A model whose match advances the query by more than one row (both sequences translated: coding2coding, ungapped:trans)
+ * is collected exactly when every model BSDP derives from it -- the terminals of every match and the join of every pair of
+ * matches -- has a compiled device family: coding2coding's have (FAM_CODING2CODING_START / _END / _JOIN, three query rows per
+ * lane), ungapped:trans's have not and keep the reference's route call for call.  An annotated sequence declines as everywhere
+ * (shim_flatten_any: the codon match's annotation veto depends on the frame).  Asked once per Heuristic. */
+static gboolean bsdp_wide_model_served(GAM *gam, Comparison *comparison){
+    static GHashTable *known = NULL;               /* Heuristic* -> 1 (no) or 2 (yes) */
+    register Heuristic *h = gam->heuristic;
+    register gint i, j, answer;
+    register gboolean ok = TRUE;
+    register gpointer ud;
+    c4gpu_model fm;
+    if(comparison->query->annotation || comparison->target->annotation)
+        return FALSE;
+    if(!known)
+        known = g_hash_table_new(g_direct_hash, g_direct_equal);
+    if((answer = GPOINTER_TO_INT(g_hash_table_lookup(known, h))))
+        return answer == 2;
+    ud = Model_Type_create_data(gam->gas->type, comparison->query, comparison->target);
+    for(i = 0; ok && (i < h->match_total); i++){
+        register Heuristic_Match *m = h->match_list[i];
+        C4_DerivedModel *dm[2];
+        dm[0] = m->start_terminal ? m->start_terminal->terminal_model : NULL;
+        dm[1] = m->end_terminal ? m->end_terminal->terminal_model : NULL;
+        for(j = 0; ok && (j < 2); j++)
+            if(dm[j] && ((!shim_flatten_any(dm[j]->derived, ud, &fm, TRUE)) || (c4gpu_model_device_family(&fm) < 0)))
+                ok = FALSE;
+        for(j = 0; ok && (j < h->match_total); j++){
+            register Heuristic_Pair *p = h->pair_matrix[i][j];
+            if(!p)
+                continue;
+            if((p->span_list && p->span_list->len)
+            || (p->join && ((!shim_flatten_any(p->join->join_model->derived, ud, &fm, TRUE))
+                         || (c4gpu_model_device_family(&fm) < 0))))
+                ok = FALSE;
+            }
+        }
+    Model_Type_destroy_data(gam->gas->type, ud);
+    g_hash_table_insert(known, h, GINT_TO_POINTER(ok ? 2 : 1));
+    return ok;
+    }
+
 GAM_Result *GAM_Result_heuristic_create(GAM *gam, Comparison *comparison){
     register ShimHPending *hp;
     register gboolean batchable = (shim_batch_size() > 0) && (!gam->gas->use_gapped_extension) && gam->heuristic
         && (bsdp_mode == BSDP_OFF)
         && (!shim_model_has_query_span(gam->heuristic->model))   /* no compiled families for a span on both axes (ner) */
-        && (!shim_model_has_wide_query_advance(gam->heuristic->model))   /* nor derived families with a query advance of 3 */
         && (!Comparison_Param_get_HSPSet_Argument_Set(comparison->param)->geneseed_threshold)
         && (shim_env("C4GPU_BSDP_HOST") || (shim_ctx_nowait() != NULL))
-        && (!shim_env("C4GPU_BSDP_OFF"));
+        && (!shim_env("C4GPU_BSDP_OFF"))
+        /* a query advance of 3: only where the derived models have device families (coding2coding; not ungapped:trans) */
+        && ((!shim_model_has_wide_query_advance(gam->heuristic->model)) || bsdp_wide_model_served(gam, comparison));
     /* --gappedextension yes: the SDP seam (c4gpu_sdp.c) takes the pairs of the models it covers */
     if(gam->gas->use_gapped_extension && (bsdp_mode == BSDP_OFF) && (!shim_sdp_replaying())
     && shim_sdp_collect(gam, comparison))

@@ -385,8 +385,9 @@ gboolean shim_flatten_any(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out, gboo
         for(j = 0; j < s->dst_transition_list->len; j++)
             o->dst_transition_mask |= ((uint64_t)1) << ((C4_Transition*)s->dst_transition_list->pdata[j])->id;
         }
-    /* a query advance above one: the two whole models have kernels (exhaustive seam); the models BSDP derives from them do
-     * not, and decline here instead of failing at batch creation call after call */
+    /* a query advance above one: the two whole models have kernels (exhaustive seam), and so have the models BSDP derives
+     * from coding2coding (c4gpu_bsdp.c); any other -- ungapped:trans's derived models -- has none, and declines here instead
+     * of failing at batch creation call after call */
     if(shim_model_has_wide_query_advance(m) && (c4gpu_model_device_family(out) < 0))
         return FALSE;
     return c4gpu_model_is_accelerated(out);

@@ -17,6 +17,14 @@ DERIVED = [("FAM_AFFINE_%s", "Affine%sDesc", "affine_%s"), ("FAM_EST2GENOME_FWD_
            ("FAM_PROTEIN2GENOME_%s", "Protein2Genome%sDesc", "protein2genome_%s")]
 DERIVED_FAMILIES = [(f % k.upper(), d % k, s_ % k.lower()) for f, d, s_ in DERIVED for k in ("Start", "End", "Join")]
 DERIVED_VARIANTS = [("MODE_SCORE", 0, 0, 0), ("MODE_PATH", 0, 0, 0)]
+# rows per lane of the derived kernels: one, except where the model advances the query by three rows (a lane hands its last
+# MAXAQ rows down, so it holds at least that many: WaveDP's static_assert).  Three, not four: a derived job is a few dozen rows
+# on one strip and runs T + 64 steps whatever the lanes hold, so a fourth row would be a third more work per step
+# for nothing (a strip of 192 rows covers the rectangles BSDP's ranges ask for), and at four rows the score kernels spill too
+# (profiles/codon_heuristic.md)
+DERIVED_R = {"coding2coding": 3}
+DERIVED_FAMILIES += [("FAM_CODING2CODING_%s" % k.upper(), "Coding2Coding%sDesc" % k, "coding2coding_%s" % k.lower())
+                     for k in ("Start", "End", "Join")]
 # (mode, cont, local, pack)
 VARIANTS = [("MODE_SCORE", 0, 1, 0), ("MODE_SCORE", 0, 0, 0), ("MODE_REGION", 0, 1, 1), ("MODE_REGION", 0, 1, 0),
             ("MODE_REGION", 0, 0, 1), ("MODE_REGION", 0, 0, 0),
@@ -99,7 +107,8 @@ for fam, desc, short in DERIVED_FAMILIES:
         sym = "k_%s_%s" % (short, mode[5:].lower())
         with open(os.path.join(OUT, sym + ".hip"), "w") as fh:
             fh.write('// generated by tools/gen_kernel_tus.py\n#include "../c4_launch.h"\nnamespace c4k {\n'
-                     'C4K_DEFINE_KERNEL(%s, %s, 1, %s, false, false, false, 4, false)\n}\n' % (sym, desc, mode))
+                     'C4K_DEFINE_KERNEL(%s, %s, %d, %s, false, false, false, 4, false)\n}\n'
+                     % (sym, desc, DERIVED_R.get(short.rsplit("_", 1)[0], 1), mode))
         entries.append((fam, mode, cont, local, pack, 0, sym, 0))
 # est2genome's span models: src (END cells out) and dst (START cells in); the src tables also serve the
 # CORNER/CORNER "src traceback" model (heuristic.c:469-472)
