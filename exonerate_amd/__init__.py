@@ -511,6 +511,55 @@ class Engine:
         finally:
             _lib().c4gpu_wordtab_destroy(tab)
 
+    def seed_extend(self, params, match, pairs, width, wordlen, words, emits, strings, tpos_scale, tpos_offset, tpos_modifier,
+                    seedlen, dropoff, threshold, cap=None, first_hits=None):
+        """Word scan to stored HSPs in one device call (c4gpu_seed_extend): what a fresh HSPset per pair holds after the
+        seeder has walked `strings` (the target's symbol strings, walked in order).  words as for seed_scan; emits: the
+        (pair, query position) of every emission.  Returns ([(walk index of the word hit, pair, [query_start, target_start,
+        length, score, cobs])] in walk order, {"n_hits", "n_extended", "n_below", "n_kept"}).  cap: room for that many
+        HSPs and one call only (more kept: an empty list, n_kept says how many); None: call again until they fit.
+        first_hits: a list that receives, per pair, the walk index of its first word hit or -1 (c4gpu_seed_extend_first_hits)."""
+        arr, keep = _pairs(pairs)
+        kind = {"dna2dna": _abi.MATCH_DNA2DNA, "protein2protein": _abi.MATCH_PROTEIN2PROTEIN,
+                "protein2dna": _abi.MATCH_PROTEIN2DNA}.get(match, match)
+        codes = (C.c_uint64 * max(1, len(words)))(*[c for c, _ in words])
+        first = [0]
+        for _, n in words:
+            first.append(first[-1] + n)
+        cf = (C.c_int32 * len(first))(*first)
+        tab = _lib().c4gpu_wordtab_create(self.ctx, width, wordlen, codes, cf, len(words))
+        if not tab:
+            raise _err("c4gpu_wordtab_create")
+        try:
+            if emits is not None:
+                ce = (_abi.SeedEmit * max(1, len(emits)))(*[_abi.SeedEmit(p, q) for p, q in emits])
+                if _lib().c4gpu_wordtab_set_emissions(tab, ce, len(emits)) != 0:
+                    raise _err("c4gpu_wordtab_set_emissions")
+            strs = [bytes(x) for x in strings]
+            sp = (C.c_char_p * max(1, len(strs)))(*strs)
+            sn = (C.c_int32 * max(1, len(strs)))(*[len(x) for x in strs])
+            so = (C.c_int32 * max(1, len(strs)))(*tpos_offset)
+            stats = _abi.SeedExtendStats()
+            room = 1 << 12 if cap is None else cap
+            while True:
+                out = (_abi.SeedHsp * max(1, room))()
+                if _lib().c4gpu_seed_extend(self.ctx, tab, params, kind, arr, len(pairs), sp, sn, len(strs), tpos_scale, so,
+                                            tpos_modifier, seedlen, dropoff, threshold, out, room, C.byref(stats)) != 0:
+                    raise _err("c4gpu_seed_extend")
+                if stats.n_kept <= room or cap is not None:
+                    break
+                room = stats.n_kept
+            if first_hits is not None:
+                fh = (C.c_int64 * max(1, len(pairs)))()
+                if _lib().c4gpu_seed_extend_first_hits(self.ctx, tab, fh, len(pairs)) != 0:
+                    raise _err("c4gpu_seed_extend_first_hits")
+                first_hits[:] = list(fh)[:len(pairs)]
+            n = stats.n_kept if stats.n_kept <= room else 0
+            return ([(out[i].seed, out[i].pair, out[i].hsp.aslist()) for i in range(n)],
+                    dict(n_hits=stats.n_hits, n_extended=stats.n_extended, n_below=stats.n_below, n_kept=stats.n_kept))
+        finally:
+            _lib().c4gpu_wordtab_destroy(tab)
+
     @staticmethod
     def sdp_stats(reset=False):
         """Counters of this thread's sdp() calls: kernel ms of the passes / walks, staging / host ms, jobs, reruns, unserved."""

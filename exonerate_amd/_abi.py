@@ -125,6 +125,18 @@ class Hsp(C.Structure):
         return [self.query_start, self.target_start, self.length, self.score, self.cobs]
 
 
+class SeedEmit(C.Structure):
+    _fields_ = [("pair", C.c_int32), ("query_pos", C.c_int32)]
+
+
+class SeedHsp(C.Structure):
+    _fields_ = [("seed", C.c_int64), ("pair", C.c_int32), ("hsp", Hsp)]
+
+
+class SeedExtendStats(C.Structure):
+    _fields_ = [("n_hits", C.c_int64), ("n_extended", C.c_int64), ("n_below", C.c_int64), ("n_kept", C.c_int64)]
+
+
 MATCH_DNA2DNA, MATCH_PROTEIN2PROTEIN, MATCH_PROTEIN2DNA = 0, 1, 2
 
 
@@ -221,6 +233,11 @@ PROTOTYPES = [
     ("c4gpu_wordtab_destroy", None, [C.c_void_p]),
     ("c4gpu_seed_scan", C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     ("c4gpu_wordtab_stats", None, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("c4gpu_wordtab_set_emissions", C.c_int, [C.c_void_p, C.POINTER(SeedEmit), C.c_int32]),
+    ("c4gpu_seed_extend", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_int, C.POINTER(Pair), C.c_int32,
+                                    C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
+                                    C.c_int32, C.c_int32, C.c_int32, C.POINTER(SeedHsp), C.c_int64, C.POINTER(SeedExtendStats)]),
+    ("c4gpu_seed_extend_first_hits", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),
     ("c4gpu_sdp_lattice_cells", C.c_double, [C.POINTER(Hsp), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     ("c4gpu_sdp_batch", C.c_int, [C.c_void_p, C.POINTER(Model), C.POINTER(Params), C.POINTER(Pair), C.c_int32, C.POINTER(Hsp),
                                   C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

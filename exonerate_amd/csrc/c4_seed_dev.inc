@@ -116,13 +116,212 @@ __global__ __launch_bounds__(256) void seed_fill_kernel(int n, const int *__rest
     }
 }
 
+// ---- c4gpu_seed_extend: the hits stay here and become the HSPs a fresh HSPset per pair would store ---------------------
+// The scan above gives every hit its walk index; what HSPset_seed_hsp (hspset.c:933-997) then does hit by hit depends on the
+// order only through the horizon entry the seed is tested against (:939-958) and moves (:990).  So: every hit becomes a seed
+// with the number of its entry (its slot: all entries of all pairs numbered through, slot_base[pair] + section * at + tf, or
+// n_slots for a seed without one); a stable radix sort groups the walk indices by slot, walk order kept inside a slot; one
+// lane per run of equal slots replays that entry alone (running horizon, hsp_extend_one); a prefix sum over the kept
+// verdicts in walk-index order lays the kept HSPs out as HSP_store met them.
+
+// seed_fill_kernel with the seed and its slot in place of the hit
+__global__ __launch_bounds__(256) void seed_expand_kernel(int n, const int *__restrict__ cnt, const int *__restrict__ first,
+                                                          const unsigned long long *__restrict__ blockoff, unsigned long long hit_base,
+                                                          unsigned long long n_hits, const c4gpu_seed_emit *__restrict__ emits,
+                                                          const HspJob *__restrict__ jobs, const unsigned *__restrict__ slot_base,
+                                                          int scale, int offset, int modifier, int at, int seedlen, unsigned n_slots,
+                                                          c4gpu_hsp_seed *__restrict__ seeds, unsigned *__restrict__ keys,
+                                                          int *__restrict__ vals, unsigned long long *__restrict__ outside,
+                                                          unsigned long long *__restrict__ first_hit) {
+    __shared__ unsigned long long part[256];
+    const int items = 8;
+    const long long base = ((long long)blockIdx.x * 256 + threadIdx.x) * items;
+    unsigned long long mine = 0;
+    for (int k = 0; k < items; k++) if (base + k < n) mine += (unsigned)cnt[base + k];
+    part[threadIdx.x] = mine;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+        const unsigned long long add = (int)threadIdx.x >= off ? part[threadIdx.x - off] : 0;
+        __syncthreads();
+        part[threadIdx.x] += add;
+        __syncthreads();
+    }
+    unsigned long long pos = hit_base + blockoff[blockIdx.x] + part[threadIdx.x] - mine;
+    for (int k = 0; k < items; k++) {
+        const long long i = base + k;
+        if (i >= n) break;
+        const int c = cnt[i], f = first[i];
+        const int ts = (int)i * scale + offset - modifier;
+        for (int e = 0; e < c; e++, pos++) {
+            if (pos >= n_hits) continue;
+            const c4gpu_seed_emit em = emits[f + e];
+            const HspJob jb = jobs[em.pair];
+            if (pos < first_hit[em.pair]) atomicMin(&first_hit[em.pair], pos);      // (it only ever falls: a stale read is too large)
+            unsigned key = n_slots;
+            int pair = em.pair;
+            if (ts < 0 || jb.qlen <= 0 || em.query_pos + seedlen > jb.qlen || (long long)ts + (long long)seedlen * at > jb.tlen) {
+                *outside = 1;                                            // the call fails; the seed is never read through
+                pair = -1;
+            } else {
+                const int diag = ts - em.query_pos * at;                 // hspset.c:941-944 (query advance 1)
+                const int section = (diag + jb.qlen) % jb.qlen;          // C's remainder: negative above the main diagonal's reach
+                if (section >= 0) key = slot_base[em.pair] + (unsigned)section * (unsigned)at + (unsigned)(ts % at);
+            }
+            seeds[pos] = c4gpu_hsp_seed{pair, em.query_pos, ts};
+            keys[pos] = key;
+            vals[pos] = (int)pos;
+        }
+    }
+}
+
+// LSD radix sort, 8 bits a pass, one wave per tile of 2048: digit histogram (hist[digit * n_blocks + block], so that one
+// exclusive scan over the whole array -- seed_blockscan_kernel -- is every (digit, block)'s place), then a stable scatter
+constexpr int SEED_SORT_TILE = 64 * 32;
+
+__global__ __launch_bounds__(64) void seed_sort_hist_kernel(const unsigned *__restrict__ keys, long long n, int shift, int n_blocks,
+                                                            unsigned long long *__restrict__ hist) {
+    __shared__ unsigned h[256];
+    for (int x = threadIdx.x; x < 256; x += 64) h[x] = 0;
+    __syncthreads();
+    const long long base = (long long)blockIdx.x * SEED_SORT_TILE;
+    for (int k = 0; k < 32; k++) {
+        const long long i = base + k * 64 + threadIdx.x;
+        if (i < n) atomicAdd(&h[(keys[i] >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    for (int x = threadIdx.x; x < 256; x += 64) hist[(size_t)x * n_blocks + blockIdx.x] = h[x];
+}
+
+__global__ __launch_bounds__(64) void seed_sort_scatter_kernel(const unsigned *__restrict__ keys, const int *__restrict__ vals, long long n,
+                                                               int shift, int n_blocks, const unsigned long long *__restrict__ hist,
+                                                               unsigned *__restrict__ keys_out, int *__restrict__ vals_out) {
+    __shared__ unsigned long long off[256];
+    for (int x = threadIdx.x; x < 256; x += 64) off[x] = hist[(size_t)x * n_blocks + blockIdx.x];
+    __syncthreads();
+    const unsigned long long below = (1ull << threadIdx.x) - 1;         // the lanes in front of this one
+    const long long base = (long long)blockIdx.x * SEED_SORT_TILE;
+    for (int k = 0; k < 32; k++) {                                       // 64 keys at a time, in order: stable
+        const long long i = base + k * 64 + threadIdx.x;
+        const bool active = i < n;
+        const unsigned key = active ? keys[i] : 0u;
+        const unsigned d = (key >> shift) & 255u;
+        unsigned long long same = __ballot(active);                      // the active lanes that hold this lane's digit
+        for (int b = 0; b < 8; b++) {
+            const bool bit = (d >> b) & 1u;
+            const unsigned long long set = __ballot(active && bit);
+            same &= bit ? set : ~set;
+        }
+        unsigned long long dst = 0;
+        if (active) dst = off[d] + (unsigned)__popcll(same & below);
+        __syncthreads();
+        if (active && !(same & below)) off[d] += (unsigned)__popcll(same);
+        __syncthreads();
+        if (active && dst < (unsigned long long)n) { keys_out[dst] = key; vals_out[dst] = vals[i]; }
+    }
+}
+
+// One lane per run of equal slots in the sorted list (a seed without a horizon entry is a run of its own): HSPset_seed_hsp
+// seed by seed on that entry alone.  verdict[k] of walk index k: 0 skipped, 1 extended and below the threshold, 2 kept.
+__global__ void seed_chain_kernel(const uint8_t *__restrict__ qcode, const uint8_t *__restrict__ tcode, const HspJob *__restrict__ jobs,
+                                  const c4gpu_hsp_seed *__restrict__ seeds, const unsigned *__restrict__ keys,
+                                  const int *__restrict__ order, long long n, unsigned n_slots, const int *__restrict__ submat, int aq,
+                                  int at, int seedlen, int dropoff, int threshold, uint8_t *__restrict__ verdict,
+                                  c4gpu_hsp *__restrict__ hsps) {
+    __shared__ int sm[24 * 24];
+    for (int x = threadIdx.x; x < 24 * 24; x += blockDim.x) sm[x] = submat[x];
+    __syncthreads();
+    for (long long x = blockIdx.x * (long long)blockDim.x + threadIdx.x; x < n; x += (long long)gridDim.x * blockDim.x) {
+        const unsigned key = keys[x];
+        const bool entry = key != n_slots;
+        if (entry && x > 0 && keys[x - 1] == key) continue;              // not the first of its run
+        int horizon = 0;                                                 // a fresh set's entries start at 0
+        for (long long y = x; y < n && keys[y] == key; y++) {
+            const int k = order[y];
+            const c4gpu_hsp_seed sd = seeds[k];
+            if (sd.pair < 0 || (entry && sd.target_start < horizon)) verdict[k] = 0;                     // hspset.c:952-958
+            else {
+                const c4gpu_hsp h = hsp_extend_one(qcode, tcode, jobs[sd.pair], sd, sm, aq, at, seedlen, dropoff);
+                hsps[k] = h;
+                verdict[k] = h.score >= threshold ? 2 : 1;               // HSP_store
+                horizon = h.target_start + h.length * at;                // HSP_target_end, :990 (stored or not)
+            }
+            if (!entry) break;
+        }
+    }
+}
+
+// kept HSPs per block of 2048 walk indices (for the prefix sum) and the number of extended seeds below the threshold
+__global__ __launch_bounds__(256) void seed_verdict_count_kernel(const uint8_t *__restrict__ verdict, long long n,
+                                                                 unsigned long long *__restrict__ blocksum,
+                                                                 unsigned long long *__restrict__ n_below) {
+    __shared__ unsigned kept[256], under[256];
+    const int items = 8;
+    const long long base = ((long long)blockIdx.x * 256 + threadIdx.x) * items;
+    unsigned a = 0, b = 0;
+    for (int k = 0; k < items; k++)
+        if (base + k < n) { const int v = verdict[base + k]; a += v == 2; b += v == 1; }
+    kept[threadIdx.x] = a; under[threadIdx.x] = b;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) { kept[threadIdx.x] += kept[threadIdx.x + off]; under[threadIdx.x] += under[threadIdx.x + off]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        blocksum[blockIdx.x] = kept[0];
+        if (under[0]) atomicAdd(n_below, (unsigned long long)under[0]);
+    }
+}
+
+// the kept HSPs to their places, in walk-index order
+__global__ __launch_bounds__(256) void seed_compact_kernel(const uint8_t *__restrict__ verdict, long long n,
+                                                           const unsigned long long *__restrict__ blockoff,
+                                                           const c4gpu_hsp_seed *__restrict__ seeds, const c4gpu_hsp *__restrict__ hsps,
+                                                           c4gpu_seed_hsp *__restrict__ out, unsigned long long cap) {
+    __shared__ unsigned part[256];
+    const int items = 8;
+    const long long base = ((long long)blockIdx.x * 256 + threadIdx.x) * items;
+    unsigned mine = 0;
+    for (int k = 0; k < items; k++) if (base + k < n) mine += verdict[base + k] == 2;
+    part[threadIdx.x] = mine;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+        const unsigned add = (int)threadIdx.x >= off ? part[threadIdx.x - off] : 0;
+        __syncthreads();
+        part[threadIdx.x] += add;
+        __syncthreads();
+    }
+    unsigned long long pos = blockoff[blockIdx.x] + part[threadIdx.x] - mine;
+    for (int k = 0; k < items; k++) {
+        const long long i = base + k;
+        if (i >= n) break;
+        if (verdict[i] != 2) continue;
+        if (pos < cap) out[pos] = c4gpu_seed_hsp{(int64_t)i, seeds[i].pair, hsps[i]};
+        pos++;
+    }
+}
+
 }  // namespace
 
 struct c4gpu_wordtab {
     c4gpu_ctx *ctx;
     int width, wordlen, n_words;
+    int n_emissions = 0;                   // emit_first[n_words]: what c4gpu_wordtab_set_emissions must bring
     unsigned mask;
     DevBuf<WordSlot> slots;
+    // c4gpu_seed_extend: the emissions (c4gpu_wordtab_set_emissions) and its scratch
+    bool emits_set = false;
+    int emit_max_pair = -1;
+    DevBuf<c4gpu_seed_emit> d_emits;
+    DevBuf<c4gpu_hsp_seed> d_seeds;
+    DevBuf<unsigned> d_keys[2], d_slot_base;
+    DevBuf<int> d_vals[2], d_submat;
+    DevBuf<unsigned long long> d_hist, d_report, d_first_hit;
+    int first_hit_pairs = -1;              // pairs of the last c4gpu_seed_extend call (-1: none yet), and whether it had hits
+    bool first_hit_any = false;
+    DevBuf<uint8_t> d_verdict;
+    DevBuf<c4gpu_hsp> d_hsps;
+    DevBuf<c4gpu_seed_hsp> d_out;
+    DevBuf<HspJob> d_jobs;
     // scratch kept between scans of one seeder (targets of similar size follow each other)
     DevBuf<uint8_t> d_sym;
     DevBuf<int> d_cnt, d_first;
@@ -142,6 +341,7 @@ extern "C" c4gpu_wordtab *c4gpu_wordtab_create(c4gpu_ctx *ctx, int32_t width, in
     try {
         std::unique_ptr<c4gpu_wordtab> t(new c4gpu_wordtab);
         t->ctx = ctx; t->width = width; t->wordlen = wordlen; t->n_words = n_words;
+        t->n_emissions = n_words > 0 ? emit_first[n_words] : 0;
         unsigned size = 16;
         while (size < 2u * (unsigned)std::max(1, n_words)) size <<= 1;
         t->mask = size - 1;
@@ -221,4 +421,165 @@ extern "C" void c4gpu_wordtab_stats(const c4gpu_wordtab *t, double *scan_ms, int
     if (scans) *scans = t->scans;
     if (symbols) *symbols = t->symbols;
     if (hits) *hits = t->hits;
+}
+
+extern "C" int c4gpu_wordtab_set_emissions(c4gpu_wordtab *t, const c4gpu_seed_emit *emits, int32_t n_emits) {
+    c4gpu_ctx *ctx = t->ctx;
+    if (hipSetDevice(ctx->device) != hipSuccess) { c4h::set_error("hipSetDevice failed"); return -1; }
+    t->emits_set = false;
+    if (n_emits != t->n_emissions) {
+        c4h::set_error("c4gpu_wordtab_set_emissions: the table's words report " + std::to_string(t->n_emissions) + " emissions, " +
+                       std::to_string(n_emits) + " given");
+        return -1;
+    }
+    int max_pair = -1;
+    for (int e = 0; e < n_emits; e++) {
+        if (emits[e].pair < 0 || emits[e].query_pos < 0) {
+            c4h::set_error("c4gpu_wordtab_set_emissions: an emission names a negative pair or query position");
+            return -1;
+        }
+        max_pair = std::max(max_pair, emits[e].pair);
+    }
+    if (t->d_emits.upload(emits, (size_t)n_emits, ctx->stream)) return -1;
+    HIP_OK(c4_stream_sync(ctx->stream));
+    t->emits_set = true;
+    t->emit_max_pair = max_pair;
+    return 0;
+}
+
+extern "C" int c4gpu_seed_extend(c4gpu_ctx *ctx, c4gpu_wordtab *t, const c4gpu_params *params, int match_type,
+                                 const c4gpu_pair *pairs, int32_t n_pairs, const uint8_t *const *symbols, const int32_t *n_symbols,
+                                 int32_t n_strings, int32_t tpos_scale, const int32_t *tpos_offset, int32_t tpos_modifier,
+                                 int32_t seedlen, int32_t dropoff, int32_t threshold, c4gpu_seed_hsp *out, int64_t cap,
+                                 c4gpu_seed_extend_stats *stats) {
+    try {
+        *stats = c4gpu_seed_extend_stats{0, 0, 0, 0};
+        if (hipSetDevice(ctx->device) != hipSuccess) { c4h::set_error("hipSetDevice failed"); return -1; }
+        if (match_type < C4GPU_MATCH_DNA2DNA || match_type > C4GPU_MATCH_PROTEIN2DNA) { c4h::set_error("unknown match type"); return -1; }
+        if (!t->emits_set) { c4h::set_error("c4gpu_seed_extend: no emissions set (c4gpu_wordtab_set_emissions)"); return -1; }
+        if (t->emit_max_pair >= n_pairs) { c4h::set_error("c4gpu_seed_extend: an emission names a pair outside `pairs`"); return -1; }
+        if (n_pairs < 0 || n_strings < 0 || tpos_scale < 1 || seedlen < 1) { c4h::set_error("c4gpu_seed_extend: bad shape"); return -1; }
+        for (int i = 1; i < n_pairs; i++)
+            if (pairs[i].target != pairs[0].target || pairs[i].target_len != pairs[0].target_len) {
+                c4h::set_error("c4gpu_seed_extend: the pairs do not all name one target buffer and length");
+                return -1;
+            }
+        const int aq = 1, at = match_type == C4GPU_MATCH_PROTEIN2DNA ? 3 : 1;
+        long long n_slots = 0;
+        std::vector<unsigned> slot_base((size_t)std::max(1, n_pairs));
+        for (int i = 0; i < n_pairs; i++) {
+            slot_base[i] = (unsigned)n_slots;
+            n_slots += (long long)std::max(0, pairs[i].query_len) * at;
+            if (n_slots > 0x7fffffffLL) { c4h::set_error("c4gpu_seed_extend: more than 2^31 - 1 horizon entries"); return -1; }
+        }
+        // the strings behind each other in one buffer, each with whole count blocks of its own
+        const int per_block = 256 * 8;
+        std::vector<size_t> sym_off((size_t)n_strings + 1, 0), blk_off((size_t)n_strings + 1, 0);
+        for (int s = 0; s < n_strings; s++) {
+            const size_t n = (size_t)std::max(0, n_symbols[s]);
+            sym_off[s + 1] = sym_off[s] + n;
+            blk_off[s + 1] = blk_off[s] + (n + per_block - 1) / per_block;
+        }
+        const size_t total_sym = sym_off[n_strings];
+        t->first_hit_pairs = n_pairs; t->first_hit_any = false;
+        if (!total_sym || !n_pairs || !t->n_emissions) return 0;
+        ResidentSeqs seqs;
+        if (seqs.build(ctx, match_type == C4GPU_MATCH_PROTEIN2DNA ? FAM_UNGAPPED_P2D : FAM_UNGAPPED, params, pairs, n_pairs)) return -1;
+        std::vector<HspJob> jobs(n_pairs);
+        for (int i = 0; i < n_pairs; i++) jobs[i] = HspJob{seqs.qoff[i], seqs.toff[i], seqs.qlen[i], seqs.tlen[i]};
+        const int32_t *mat = match_type == C4GPU_MATCH_DNA2DNA ? &params->dna_submat[0][0] : &params->protein_submat[0][0];
+        hipStream_t s = ctx->stream;
+        std::vector<unsigned long long> totals((size_t)n_strings, 0), hit_base((size_t)n_strings + 1, 0);
+        std::vector<uint8_t> hsym(total_sym);
+        for (int k = 0; k < n_strings; k++)
+            if (sym_off[k + 1] > sym_off[k]) memcpy(hsym.data() + sym_off[k], symbols[k], sym_off[k + 1] - sym_off[k]);
+        if (t->d_jobs.upload(jobs.data(), n_pairs, s) || t->d_slot_base.upload(slot_base.data(), n_pairs, s) ||
+            t->d_submat.upload(mat, 24 * 24, s) || t->d_sym.upload(hsym.data(), total_sym, s) || t->d_cnt.alloc(total_sym) ||
+            t->d_first.alloc(total_sym) || t->d_blocksum.alloc(blk_off[n_strings]) || t->d_total.upload(totals.data(), (size_t)n_strings, s)) return -1;
+        // 1. count: per string, as c4gpu_seed_scan
+        for (int k = 0; k < n_strings; k++) {
+            const int n = (int)(sym_off[k + 1] - sym_off[k]), n_blocks = (int)(blk_off[k + 1] - blk_off[k]);
+            if (!n) continue;
+            hipLaunchKernelGGL(seed_count_kernel, dim3(n_blocks), dim3(256), 0, s, t->d_sym.p + sym_off[k], n, t->width, t->wordlen,
+                               t->slots.p, t->mask, t->d_cnt.p + sym_off[k], t->d_first.p + sym_off[k], t->d_blocksum.p + blk_off[k]);
+            hipLaunchKernelGGL(seed_blockscan_kernel, dim3(1), dim3(1024), 0, s, t->d_blocksum.p + blk_off[k], n_blocks, t->d_total.p + k);
+        }
+        HIP_OK(hipGetLastError());
+        if (t->d_total.download(totals.data(), (size_t)n_strings, s)) return -1;     // 8 bytes per string: they size the buffers
+        HIP_OK(c4_stream_sync(s));
+        for (int k = 0; k < n_strings; k++) hit_base[k + 1] = hit_base[k] + totals[k];
+        const unsigned long long n_hits = hit_base[n_strings];
+        t->scans += n_strings; t->symbols += (long long)total_sym; t->hits += (long long)n_hits;
+        stats->n_hits = (int64_t)n_hits;
+        if (n_hits > 0x7fffffffULL) { c4h::set_error("c4gpu_seed_extend: more than 2^31 - 1 word hits"); return -1; }
+        if (!n_hits) return 0;
+        const long long N = (long long)n_hits;
+        const int n_tiles = (int)((N + SEED_SORT_TILE - 1) / SEED_SORT_TILE);          // sort tiles and verdict blocks: 2048 each
+        const unsigned long long cap_dev = (unsigned long long)std::min<long long>(std::max<int64_t>(cap, 0), N);
+        const unsigned long long zero4[4] = {0, 0, 0, 0};                             // outside flag, below, kept, (scan scratch)
+        if (t->d_seeds.alloc(N) || t->d_keys[0].alloc(N) || t->d_keys[1].alloc(N) || t->d_vals[0].alloc(N) || t->d_vals[1].alloc(N) ||
+            t->d_verdict.alloc(N) || t->d_hsps.alloc(N) || t->d_hist.alloc((size_t)256 * n_tiles) || t->d_report.upload(zero4, 4, s) ||
+            t->d_out.alloc((size_t)std::max<unsigned long long>(cap_dev, 1))) return -1;
+        {
+            const std::vector<unsigned long long> none((size_t)n_pairs, ~0ull);
+            if (t->d_first_hit.upload(none.data(), (size_t)n_pairs, s)) return -1;
+            HIP_OK(c4_stream_sync(s));                                                // (`none` goes away)
+        }
+        // 2. expand
+        for (int k = 0; k < n_strings; k++) {
+            const int n = (int)(sym_off[k + 1] - sym_off[k]), n_blocks = (int)(blk_off[k + 1] - blk_off[k]);
+            if (!n || !totals[k]) continue;
+            hipLaunchKernelGGL(seed_expand_kernel, dim3(n_blocks), dim3(256), 0, s, n, t->d_cnt.p + sym_off[k], t->d_first.p + sym_off[k],
+                               t->d_blocksum.p + blk_off[k], hit_base[k], n_hits, t->d_emits.p, t->d_jobs.p, t->d_slot_base.p, tpos_scale,
+                               tpos_offset ? tpos_offset[k] : 0, tpos_modifier, at, seedlen, (unsigned)n_slots, t->d_seeds.p,
+                               t->d_keys[0].p, t->d_vals[0].p, t->d_report.p, t->d_first_hit.p);
+        }
+        // 3. group by slot: keys run to n_slots (the seeds without an entry)
+        int passes = 0, cur = 0;
+        for (unsigned long long v = (unsigned long long)n_slots; v; v >>= 8) passes++;
+        for (int p = 0; p < passes; p++, cur ^= 1) {
+            hipLaunchKernelGGL(seed_sort_hist_kernel, dim3(n_tiles), dim3(64), 0, s, t->d_keys[cur].p, N, 8 * p, n_tiles, t->d_hist.p);
+            hipLaunchKernelGGL(seed_blockscan_kernel, dim3(1), dim3(1024), 0, s, t->d_hist.p, 256 * n_tiles, t->d_report.p + 3);
+            hipLaunchKernelGGL(seed_sort_scatter_kernel, dim3(n_tiles), dim3(64), 0, s, t->d_keys[cur].p, t->d_vals[cur].p, N, 8 * p, n_tiles,
+                               t->d_hist.p, t->d_keys[cur ^ 1].p, t->d_vals[cur ^ 1].p);
+        }
+        // 4. chains, 5. compaction
+        const int chain_grid = (int)std::min<long long>((N + 63) / 64, 1 << 20);
+        hipLaunchKernelGGL(seed_chain_kernel, dim3(chain_grid), dim3(64), 0, s, seqs.qcode.p, seqs.tcode.p, t->d_jobs.p, t->d_seeds.p,
+                           t->d_keys[cur].p, t->d_vals[cur].p, N, (unsigned)n_slots, t->d_submat.p, aq, at, seedlen, dropoff, threshold,
+                           t->d_verdict.p, t->d_hsps.p);
+        hipLaunchKernelGGL(seed_verdict_count_kernel, dim3(n_tiles), dim3(256), 0, s, t->d_verdict.p, N, t->d_hist.p, t->d_report.p + 1);
+        hipLaunchKernelGGL(seed_blockscan_kernel, dim3(1), dim3(1024), 0, s, t->d_hist.p, n_tiles, t->d_report.p + 2);
+        hipLaunchKernelGGL(seed_compact_kernel, dim3(n_tiles), dim3(256), 0, s, t->d_verdict.p, N, t->d_hist.p, t->d_seeds.p, t->d_hsps.p,
+                           t->d_out.p, cap_dev);
+        HIP_OK(hipGetLastError());
+        unsigned long long report[3] = {0, 0, 0};
+        if (t->d_report.download(report, 3, s)) return -1;
+        HIP_OK(c4_stream_sync(s));
+        if (report[0]) { c4h::set_error("c4gpu_seed_extend: a seed does not lie inside its pair"); return -1; }
+        t->first_hit_any = true;
+        stats->n_below = (int64_t)report[1];
+        stats->n_kept = (int64_t)report[2];
+        stats->n_extended = stats->n_below + stats->n_kept;
+        if (stats->n_kept > cap) return 0;                                  // the caller comes back with room for all of them
+        if (stats->n_kept) { if (t->d_out.download(out, (size_t)stats->n_kept, s)) return -1; HIP_OK(c4_stream_sync(s)); }
+        return 0;
+    } catch (const std::exception &e) {
+        c4h::set_error(std::string("c4gpu_seed_extend: ") + e.what());
+        return -1;
+    }
+}
+
+extern "C" int c4gpu_seed_extend_first_hits(c4gpu_ctx *ctx, c4gpu_wordtab *t, int64_t *first_hit, int32_t n_pairs) {
+    if (hipSetDevice(ctx->device) != hipSuccess) { c4h::set_error("hipSetDevice failed"); return -1; }
+    if (t->first_hit_pairs < 0 || n_pairs != t->first_hit_pairs) {
+        c4h::set_error("c4gpu_seed_extend_first_hits: no c4gpu_seed_extend call over that many pairs came before");
+        return -1;
+    }
+    for (int i = 0; i < n_pairs; i++) first_hit[i] = -1;
+    if (!t->first_hit_any || !n_pairs) return 0;
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "first hits are downloaded in place");
+    if (t->d_first_hit.download(reinterpret_cast<unsigned long long *>(first_hit), (size_t)n_pairs, ctx->stream)) return -1;
+    HIP_OK(c4_stream_sync(ctx->stream));                                              // (no hit: ~0 is -1)
+    return 0;
 }

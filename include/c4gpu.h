@@ -18,6 +18,7 @@
  *   c4gpu_alignment_display / _format_gff / _format_ryo  <->  Alignment_display / _display_gff / _display_ryo  src/c4/alignment.c:1343,3212,2659
  *   c4gpu_batch_run_regions  <->  Optimal_find_path with a region (--refine)   src/hub/gam.c:605-655
  *   c4gpu_seed_scan          <->  Seeder_add_target's automaton walk src/comparison/seeder.c:649-720,852-915
+ *   c4gpu_seed_extend        <->  that walk with Seeder_WordInfo_seed and HSPset_seed_hsp behind it  seeder.c:624-647, hspset.c:933-997
  *   c4gpu_sdp_batch          <->  GAM_Result_SDP_create's loop (SDP_Pair_next_path) src/hub/gam.c:852-890, src/sdp/sdp.c:743
  */
 #ifndef INCLUDED_C4GPU_H
@@ -516,6 +517,43 @@ int         c4gpu_seed_scan(c4gpu_ctx *ctx, c4gpu_wordtab *t, const uint8_t *sym
                             int64_t cap, int64_t *n_hits);
 /* device time of the scans of a table (HIP events), their number, symbols scanned, hits found */
 void        c4gpu_wordtab_stats(const c4gpu_wordtab *t, double *scan_ms, int64_t *scans, int64_t *symbols, int64_t *hits);
+
+/* Word scan to stored HSPs in one call, the hits staying on the device: what one fresh HSPset per pair holds after
+ * Seeder_add_target (seeder.c:852-915) has walked the target -- Seeder_WordInfo_seed (seeder.c:624-647) handing every hit to
+ * HSPset_seed_hsp (hspset.c:933-997: horizon test :939-958, extension, HSP_store's threshold, horizon update :990), for
+ * seed_repeat 1 and sets without soft-masking (those keep c4gpu_hsp_extend_*_masked).
+ * c4gpu_wordtab_set_emissions tells the table what its emissions are: emission e seeds the HSPset of pairs[emits[e].pair]
+ * at query position emits[e].query_pos (n_emits = emit_first[n_words] of the table).
+ * c4gpu_seed_extend walks `n_strings` symbol strings in order (one target, or its three translated frames), each as
+ * c4gpu_seed_scan does; hit k of string s at `pos` with emission e is the seed
+ *     pair = emits[e].pair, query_start = emits[e].query_pos, target_start = pos * tpos_scale + tpos_offset[s] - tpos_modifier
+ * (untranslated: scale 1, offset 0, modifier wordlen - 1, Seeder_Loader_create; translated: scale 3, offset frame - 1,
+ * modifier wordlen * 3 - 3, Seeder_FSM_traverse_func seeder.c:657-660).  All pairs name one target buffer and length.
+ * Horizon: at = 3 for PROTEIN2DNA, else 1; diag = target_start - query_start * at; section = (diag + qlen) % qlen with C's
+ * truncating remainder; tf = target_start % at.  A seed with section < 0 has no horizon entry: always extended, updates
+ * nothing.  Every other seed is skipped when target_start lies below entry (pair, section, tf) -- keyed by SECTION as in the
+ * reference, so protein-vs-DNA diagonals qlen bases apart share one -- and otherwise extended; the entry becomes
+ * hsp.target_start + hsp.length * at whether or not the HSP reaches `threshold`.  Kept = extended with score >= threshold
+ * (HSP_store).  out: the kept HSPs in walk order, `seed` = index of the word hit in walk order over all strings; when
+ * stats->n_kept exceeds cap nothing is written and the call returns 0 (come back with more room, as for c4gpu_seed_scan).
+ * Fails (-1): unknown match type; no emissions set or their number is not the table's; an emission naming no pair or a
+ * negative query position; pairs of different targets; a seed outside its pair; more than 2^31 - 1 hits or horizon entries;
+ * a residue outside the submat alphabet. */
+typedef struct { int32_t pair, query_pos; } c4gpu_seed_emit;
+int         c4gpu_wordtab_set_emissions(c4gpu_wordtab *t, const c4gpu_seed_emit *emits, int32_t n_emits);
+typedef struct { int64_t seed; int32_t pair; c4gpu_hsp hsp; } c4gpu_seed_hsp;
+typedef struct { int64_t n_hits, n_extended, n_below, n_kept; } c4gpu_seed_extend_stats;
+int         c4gpu_seed_extend(c4gpu_ctx *ctx, c4gpu_wordtab *t, const c4gpu_params *params, int match_type,
+                              const c4gpu_pair *pairs, int32_t n_pairs,
+                              const uint8_t *const *symbols, const int32_t *n_symbols, int32_t n_strings,
+                              int32_t tpos_scale, const int32_t *tpos_offset, int32_t tpos_modifier,
+                              int32_t seedlen, int32_t dropoff, int32_t threshold,
+                              c4gpu_seed_hsp *out, int64_t cap, c4gpu_seed_extend_stats *stats);
+/* first_hit[p]: the walk index of pair p's FIRST word hit in the last c4gpu_seed_extend call on this table (kept or not), -1:
+ * the pair had none.  Seeder_WordInfo_seed creates a query's Comparison at its first hit (seeder.c:634-640) and the report
+ * loop of Seeder_add_target (seeder.c:899-913) follows that order: a caller that reports per pair needs it.  n_pairs: that
+ * call's.  8 bytes per pair come down. */
+int         c4gpu_seed_extend_first_hits(c4gpu_ctx *ctx, c4gpu_wordtab *t, int64_t *first_hit, int32_t n_pairs);
 
 /* SDP, the default gapped-extension heuristic (SDP_Pair_next_path src/sdp/sdp.c:743 in the loop of GAM_Result_SDP_create
  * src/hub/gam.c:852-890), for every pair of a batch, in the flavour SDP_create picks for the model (sdp.c:322-366):

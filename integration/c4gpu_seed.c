@@ -17,6 +17,15 @@
  * Building the automaton (Seeder_add_query, word neighbourhoods) stays the reference's.  Not taken (the reference's own
  * function runs): --saturatethreshold (a per-word running count in walk order), --wordambiguity > 1, seeders with both
  * a DNA and a codon loader, a seeder whose automaton was compiled before this front saw it.
+ * C4GPU_SEED_FUSED=1 (opt-in): where every emission of the table belongs to one loader whose HSP_Param
+ * the seeding seam would take (a horizon, seed_repeat 1, DNA / protein / protein-vs-DNA, no soft-masked alphabet) step 2 is ONE
+ * c4gpu_seed_extend call per target -- scan, horizon test, extension and threshold on the device, the hits never leaving it --
+ * and only the HSPs a fresh HSPset per query would store come back, in walk order; each goes to HSPset_add_known_hsp of its
+ * query's set; the Comparisons are created in the order of the queries' first word hits (c4gpu_seed_extend_first_hits), which is
+ * the order Seeder_WordInfo_seed creates them in and the report loop follows.  A query whose hits all fall away gets no
+ * Comparison (the reference makes one and destroys it unreported).  With C4GPU_SEED_HOST=1 the kept list comes from the
+ * reference's own HSPset_seed_hsp on one scratch set per query, fed the host scan's seeds in order.  A call that fails leaves
+ * nothing delivered: the target takes the scan and extension calls below.  Not with C4GPU_SEED_CHECK / C4GPU_HSP_CHECK.
  * C4GPU_SEED_OFF=1 switches the seam off; C4GPU_SEED_HOST=1 replaces the device scan by a dictionary scan on the host
  * (CPU test of steps 1 and 3); C4GPU_SEED_CHECK=1 also runs the reference's own walk first and compares the two hit lists
  * seed for seed (abort on the first difference).
@@ -36,6 +45,7 @@
 #include "c4gpu_shim.h"
 
 extern void Seeder_add_target_cpu(Seeder *seeder, Sequence *target);
+extern void HSPset_seed_hsp_cpu(HSPset *hsp_set, guint query_start, guint target_start);
 extern void Seeder_destroy_cpu(Seeder *seeder);
 
 typedef struct { Seeder_QueryInfo *query_info; Seeder_Loader *loader; gint query_pos; } ShimEmit;
@@ -51,11 +61,19 @@ typedef struct {
     GArray *codes, *first, *emits;        /* guint64 per word; gint32 n_words + 1; ShimEmit */
     GHashTable *host_index;               /* C4GPU_SEED_HOST: code -> word number + 1 */
     c4gpu_wordtab *tab;
+    /* C4GPU_SEED_FUSED: the one loader all emissions belong to (NULL: several, or its HSP_Param is not served), the emissions
+     * as (index in the seeder's query list, query position), the queries' residues, whether the device table has them */
+    gboolean fused_looked;
+    Seeder_Loader *fused_loader;
+    c4gpu_seed_emit *fused_emits;
+    gchar **fused_query;
+    gboolean fused_sent;
 } ShimSeedTab;
 
 static GHashTable *seed_tabs = NULL;      /* Seeder* -> ShimSeedTab* */
 static GArray *seed_record = NULL;        /* C4GPU_SEED_CHECK: what the reference's own walk hands to HSPset_seed_hsp */
-static struct { long targets, cpu_targets, scans, symbols, hits, checked, words, emits; double scan_ms, host_ms, table_ms; } sdst;
+static struct { long targets, cpu_targets, scans, symbols, hits, checked, words, emits; double scan_ms, host_ms, table_ms;
+                long fused_targets, fused_hits, fused_extended, fused_kept; double fused_ms; } sdst;
 
 gboolean shim_seed_recording(HSPset *hsp_set, guint query_start, guint target_start){
     ShimSeedRec r;
@@ -398,6 +416,269 @@ static void seed_deliver_frame(ShimSeedTab *st, Sequence *target, ShimFrameHits 
     return;
     }
 
+/* ---- C4GPU_SEED_FUSED: scan to stored HSPs in one call ---- */
+
+static gint seed_match_kind(HSP_Param *param){
+    switch(param->match->type){
+        case Match_Type_DNA2DNA: return C4GPU_MATCH_DNA2DNA;
+        case Match_Type_PROTEIN2PROTEIN: return C4GPU_MATCH_PROTEIN2PROTEIN;
+        case Match_Type_PROTEIN2DNA: return C4GPU_MATCH_PROTEIN2DNA;
+        default: return -1;
+        }
+    }
+
+/* once per table: one loader behind every emission, its HSP_Param one the seeding seam takes (hsp_eligible, c4gpu_hsp.c) */
+static void seed_fused_look(ShimSeedTab *st){
+    register Seeder *seeder = st->seeder;
+    register GHashTable *index;
+    register Seeder_Loader *loader = NULL;
+    register guint k;
+    st->fused_looked = TRUE;
+    if(!st->emits->len)
+        return;
+    for(k = 0; k < st->emits->len; k++){
+        register ShimEmit *e = &g_array_index(st->emits, ShimEmit, k);
+        if(loader && (e->loader != loader))
+            return;
+        loader = e->loader;
+        }
+    if((!loader->hsp_param->use_horizon) || (loader->hsp_param->seed_repeat > 1) || (seed_match_kind(loader->hsp_param) < 0))
+        return;
+    index = g_hash_table_new(g_direct_hash, g_direct_equal);
+    st->fused_query = g_new0(gchar*, seeder->query_info_list->len + 1);
+    for(k = 0; k < seeder->query_info_list->len; k++){
+        register Seeder_QueryInfo *query_info = seeder->query_info_list->pdata[k];
+        g_hash_table_insert(index, query_info, GINT_TO_POINTER(k + 1));
+        st->fused_query[k] = Sequence_get_str(query_info->query);
+        if(query_info->query->alphabet->is_soft_masked)
+            loader = NULL;
+        }
+    st->fused_emits = g_new(c4gpu_seed_emit, st->emits->len);
+    for(k = 0; loader && (k < st->emits->len); k++){
+        register ShimEmit *e = &g_array_index(st->emits, ShimEmit, k);
+        register gint at = GPOINTER_TO_INT(g_hash_table_lookup(index, e->query_info));
+        if(!at)
+            loader = NULL;
+        st->fused_emits[k].pair = at - 1;
+        st->fused_emits[k].query_pos = e->query_pos;
+        }
+    g_hash_table_destroy(index);
+    st->fused_loader = loader;
+    return;
+    }
+
+static gboolean seed_fused_wanted(ShimSeedTab *st, Sequence *target){
+    static gint on = -1;
+    if(on < 0)
+        on = (shim_env("C4GPU_SEED_FUSED") && atoi(shim_env("C4GPU_SEED_FUSED")) && (!shim_env("C4GPU_SEED_CHECK"))
+              && (!shim_env("C4GPU_HSP_CHECK")) && (!shim_env("C4GPU_HSP_OFF"))) ? 1 : 0;
+    if(!on)
+        return FALSE;
+    if(!st->fused_looked)
+        seed_fused_look(st);
+    return st->fused_loader && (!target->alphabet->is_soft_masked);
+    }
+
+/* the kept list on the device: one c4gpu_seed_extend call */
+static gboolean seed_fused_device(ShimSeedTab *st, Sequence *target, gchar *tstr, guchar **sym, gint32 *n_sym, gint n_strs,
+                                  c4gpu_seed_hsp **kept, c4gpu_seed_extend_stats *stats, gint64 *first_hit){
+    register Seeder *seeder = st->seeder;
+    register HSP_Param *param = st->fused_loader->hsp_param;
+    register gint n_pairs = seeder->query_info_list->len, i;
+    register c4gpu_pair *pairs;
+    static const gint32 frame_offset[3] = {0, 1, 2};
+    register gboolean translated = param->match->target->is_translated;
+    register gboolean ok = FALSE;
+    gint64 cap = 1024;
+    c4gpu_params params;
+    if((!st->fused_sent) && (c4gpu_wordtab_set_emissions(st->tab, st->fused_emits, st->emits->len) != 0))
+        return FALSE;
+    st->fused_sent = TRUE;
+    shim_hsp_params(&params);
+    pairs = g_new0(c4gpu_pair, n_pairs + 1);
+    for(i = 0; i < n_pairs; i++){
+        register Seeder_QueryInfo *query_info = seeder->query_info_list->pdata[i];
+        pairs[i].query = (const uint8_t*)st->fused_query[i]; pairs[i].query_len = query_info->query->len;
+        pairs[i].target = (const uint8_t*)tstr;              pairs[i].target_len = target->len;
+        }
+    for(i = 0; i < n_strs; i++)
+        cap += n_sym[i] / 64;
+    for(;;){
+        *kept = g_new(c4gpu_seed_hsp, cap + 1);
+        if(c4gpu_seed_extend(shim_get_ctx(), st->tab, &params, seed_match_kind(param), pairs, n_pairs,
+                             (const uint8_t *const *)sym, n_sym, n_strs, translated ? 3 : 1, frame_offset,
+                             st->fused_loader->tpos_modifier, param->seedlen, param->dropoff, param->threshold,
+                             *kept, cap, stats) != 0)
+            break;
+        if(stats->n_kept <= cap){
+            ok = TRUE;
+            break;
+            }
+        g_free(*kept);
+        cap = stats->n_kept;
+        }
+    if(ok && (c4gpu_seed_extend_first_hits(shim_get_ctx(), st->tab, first_hit, n_pairs) != 0))
+        ok = FALSE;
+    if(!ok){
+        g_free(*kept);
+        *kept = NULL;
+        }
+    g_free(pairs);
+    return ok;
+    }
+
+/* C4GPU_SEED_HOST: the kept list from the reference's own HSPset_seed_hsp, one scratch set per query fed the host scan's seeds
+ * in order; what it stores is read as it is stored (before any finalising, which may reorder the list).  The filter queues
+ * (--hspfilter) are for the real set: the scratch sets run without them.  A seed without a horizon entry (negative section:
+ * see hsp_replay, c4gpu_hsp.c) gets a scratch set of its own. */
+static gboolean seed_fused_host(ShimSeedTab *st, Sequence *target, gchar **strs, gint *str_frame, gint n_strs,
+                                c4gpu_seed_hsp **kept, c4gpu_seed_extend_stats *stats, gint64 *first_hit){
+    register Seeder *seeder = st->seeder;
+    register HSP_Param *param = st->fused_loader->hsp_param;
+    register gint n_pairs = seeder->query_info_list->len, i, at = param->match->target->advance;
+    register HSPset **scratch = g_new0(HSPset*, n_pairs + 1);
+    register GArray *out = g_array_new(FALSE, FALSE, sizeof(c4gpu_seed_hsp));
+    register gint keep_filter = param->has->filter_threshold;
+    register gint64 k, walk = 0;
+    ShimFrameHits fh;
+    memset(stats, 0, sizeof(*stats));
+    param->has->filter_threshold = 0;
+    for(i = 0; i < n_strs; i++){
+        if(!seed_scan_string(st, strs[i], str_frame[i], &fh))
+            continue;                                               /* (the host scan does not fail) */
+        for(k = 0; k < fh.n_hits; k++, walk++){
+            register c4gpu_seed_emit *e = &st->fused_emits[fh.hits[k].emit];
+            register Seeder_QueryInfo *query_info = seeder->query_info_list->pdata[e->pair];
+            register gint tpos = (fh.frame ? (fh.hits[k].pos * 3) + fh.frame - 1 : fh.hits[k].pos) - st->fused_loader->tpos_modifier;
+            register gint qlen = query_info->query->len, diag_pos = tpos - (e->query_pos * at);
+            register gint section_pos = (diag_pos + qlen) % qlen;
+            register HSPset *set;
+            register guint before;
+            if(first_hit[e->pair] < 0)
+                first_hit[e->pair] = walk;
+            if(section_pos < 0)
+                set = HSPset_create(query_info->query, target, param);
+            else {
+                if(!scratch[e->pair])
+                    scratch[e->pair] = HSPset_create(query_info->query, target, param);
+                set = scratch[e->pair];
+                }
+            before = set->hsp_list->len;
+            if((section_pos < 0) || (tpos >= set->horizon[0][section_pos][0][tpos % at]))
+                stats->n_extended++;
+            HSPset_seed_hsp_cpu(set, e->query_pos, tpos);
+            if(set->hsp_list->len > before){
+                register HSP *h = set->hsp_list->pdata[set->hsp_list->len - 1];
+                c4gpu_seed_hsp x;
+                x.seed = walk; x.pair = e->pair;
+                x.hsp.query_start = h->query_start; x.hsp.target_start = h->target_start; x.hsp.length = h->length;
+                x.hsp.score = h->score; x.hsp.cobs = h->cobs;
+                g_array_append_val(out, x);
+                }
+            if(section_pos < 0)
+                HSPset_destroy(set);
+            }
+        g_free(fh.hits);
+        }
+    param->has->filter_threshold = keep_filter;
+    for(i = 0; i < n_pairs; i++)
+        if(scratch[i])
+            HSPset_destroy(scratch[i]);
+    g_free(scratch);
+    stats->n_hits = walk;
+    stats->n_kept = out->len;
+    stats->n_below = stats->n_extended - stats->n_kept;
+    *kept = (c4gpu_seed_hsp*)g_array_free(out, FALSE);
+    return TRUE;
+    }
+
+/* What seed_deliver does, for the HSPs that are kept.  The reference creates a query's Comparison at its first word hit, kept
+ * or not (seeder.c:634-640), and reports in that order (seeder.c:899-913): the queries that keep an HSP get theirs here in the
+ * order of their first hits, then every HSP goes to its set in walk order. */
+static gint seed_fused_order(gconstpointer a, gconstpointer b, gpointer first_hit){
+    register gint64 x = ((const gint64*)first_hit)[*(const gint*)a], y = ((const gint64*)first_hit)[*(const gint*)b];
+    return (x < y) ? -1 : ((x > y) ? 1 : 0);
+    }
+static void seed_fused_deliver(ShimSeedTab *st, Sequence *target, const c4gpu_seed_hsp *kept, const c4gpu_seed_extend_stats *stats,
+                               const gint64 *first_hit){
+    register Seeder *seeder = st->seeder;
+    register gint n_pairs = seeder->query_info_list->len, n_with = 0, i;
+    register gint *with = g_new(gint, n_pairs + 1);
+    register gboolean *has = g_new0(gboolean, n_pairs + 1);
+    register gint64 k;
+    for(k = 0; k < stats->n_kept; k++)
+        if(!has[kept[k].pair]){
+            has[kept[k].pair] = TRUE;
+            with[n_with++] = kept[k].pair;
+            }
+    g_qsort_with_data(with, n_with, sizeof(gint), seed_fused_order, (gpointer)first_hit);
+    for(i = 0; i < n_with; i++){
+        register Seeder_QueryInfo *query_info = seeder->query_info_list->pdata[with[i]];
+        if(!query_info->curr_comparison){
+            query_info->curr_comparison = Comparison_create(seeder->comparison_param, query_info->query, target);
+            g_ptr_array_add(seeder->active_queryinfo_list, query_info);
+            }
+        }
+    g_free(with);
+    g_free(has);
+    for(k = 0; k < stats->n_kept; k++){
+        register Seeder_QueryInfo *query_info = seeder->query_info_list->pdata[kept[k].pair];
+        register HSPset *hspset;
+        hspset = *(HSPset**)((gchar*)query_info->curr_comparison + st->fused_loader->hspset_offset);
+        HSPset_add_known_hsp(hspset, kept[k].hsp.query_start, kept[k].hsp.target_start, kept[k].hsp.length);
+        }
+    seeder->comparison_count += stats->n_hits;
+    return;
+    }
+
+/* TRUE: the target's HSPs are in their sets */
+static gboolean seed_fused_target(ShimSeedTab *st, Sequence *target, gchar **strs, gint *str_frame, gint n_strs){
+    c4gpu_seed_hsp *kept = NULL;
+    c4gpu_seed_extend_stats stats;
+    register gboolean ok;
+    register gint i, n_pairs = st->seeder->query_info_list->len;
+    register gint64 *first_hit = g_new(gint64, n_pairs + 1);
+    gint64 t0 = g_get_monotonic_time();
+    for(i = 0; i < n_pairs; i++)
+        first_hit[i] = -1;
+    if(st->host_index)
+        ok = seed_fused_host(st, target, strs, str_frame, n_strs, &kept, &stats, first_hit);
+    else {
+        guchar *sym[3];
+        gint32 n_sym[3];
+        register gchar *tstr = Sequence_get_str(target);
+        for(i = 0; i < n_strs; i++){
+            register gint n = strlen(strs[i]), x;
+            sym[i] = g_new(guchar, n + 1);
+            for(x = 0; x < n; x++)
+                sym[i][x] = st->column[(guchar)strs[i][x]];
+            n_sym[i] = n;
+            }
+        ok = seed_fused_device(st, target, tstr, sym, n_sym, n_strs, &kept, &stats, first_hit);
+        for(i = 0; i < n_strs; i++){
+            g_free(sym[i]);
+            if(ok){
+                sdst.scans++; sdst.symbols += n_sym[i];
+                }
+            }
+        if(ok)
+            sdst.hits += stats.n_hits;
+        g_free(tstr);
+        if(!ok)
+            g_warning("c4gpu: %s -- this target takes the scan and extension calls", c4gpu_last_error());
+        }
+    if(!ok){
+        g_free(first_hit);
+        return FALSE;
+        }
+    seed_fused_deliver(st, target, kept, &stats, first_hit);
+    g_free(kept);
+    g_free(first_hit);
+    sdst.fused_targets++; sdst.fused_hits += stats.n_hits; sdst.fused_extended += stats.n_extended; sdst.fused_kept += stats.n_kept;
+    sdst.fused_ms += (g_get_monotonic_time() - t0) / 1e3;
+    return TRUE;
+    }
+
 void Seeder_add_target(Seeder *seeder, Sequence *target){
     register ShimSeedTab *st = NULL;
     register Match *match = seeder->any_hsp_param->match;
@@ -405,8 +686,10 @@ void Seeder_add_target(Seeder *seeder, Sequence *target){
     register Seeder_QueryInfo *query_info;
     register GArray *mine = NULL, *theirs = NULL;
     ShimFrameHits frames[3];
+    gchar *strs[3];
+    gint str_frame[3], n_strs = 0;
     gint n_frames = 0;
-    gboolean ok = TRUE;
+    gboolean ok = TRUE, fused = FALSE;
     static gint off = -1;
     if(off < 0)
         off = (shim_env("C4GPU_SEED_OFF") || (shim_batch_size() <= 0)) ? 1 : 0;
@@ -443,26 +726,30 @@ void Seeder_add_target(Seeder *seeder, Sequence *target){
     sdst.targets++;
     Sequence_share(target);
     if(match->target->is_translated){                          /* seeder.c:868-884 */
-        for(i = 0; (i < 3) && ok; i++){
+        for(i = 0; i < 3; i++){
             register Sequence *aa_seq = Sequence_translate(target, match->mas->translate, i + 1);
             register Sequence *masked = Sequence_mask(aa_seq);
-            register gchar *seq = Sequence_get_str(masked);
+            strs[n_strs] = Sequence_get_str(masked);
+            str_frame[n_strs++] = i + 1;
             Sequence_destroy(aa_seq);
             Sequence_destroy(masked);
-            ok = seed_scan_string(st, seq, i + 1, &frames[n_frames]);
-            if(ok)
-                n_frames++;
-            g_free(seq);
             }
     } else {
         register Sequence *masked = Sequence_mask(target);
-        register gchar *seq = Sequence_get_str(masked);
+        strs[0] = Sequence_get_str(masked);
+        str_frame[0] = 0;
+        n_strs = 1;
         Sequence_destroy(masked);
-        ok = seed_scan_string(st, seq, 0, &frames[0]);
-        if(ok)
-            n_frames = 1;
-        g_free(seq);
         }
+    if(seed_fused_wanted(st, target))
+        fused = seed_fused_target(st, target, strs, str_frame, n_strs);
+    for(i = 0; (i < n_strs) && ok && (!fused); i++){
+        ok = seed_scan_string(st, strs[i], str_frame[i], &frames[n_frames]);
+        if(ok)
+            n_frames++;
+        }
+    for(i = 0; i < n_strs; i++)
+        g_free(strs[i]);
     if(!ok){
         /* nothing has been delivered yet: this target (and the rest of this seeder's) keeps the reference's walk */
         for(i = 0; i < n_frames; i++)
@@ -519,6 +806,13 @@ void Seeder_destroy(Seeder *seeder){
             c4gpu_wordtab_destroy(st->tab);
         if(st->host_index)
             g_hash_table_destroy(st->host_index);
+        if(st->fused_query){
+            register guint k;
+            for(k = 0; st->fused_query[k]; k++)
+                g_free(st->fused_query[k]);
+            g_free(st->fused_query);
+            }
+        g_free(st->fused_emits);
         if(st->codes){
             g_array_free(st->codes, TRUE); g_array_free(st->first, TRUE); g_array_free(st->emits, TRUE);
             }
@@ -537,5 +831,8 @@ void shim_seed_report(void){
                   "delivery %.0f ms, word tables (%ld words, %ld emissions) %.0f ms%s", sdst.targets, sdst.scans, sdst.symbols,
                   sdst.hits, sdst.scan_ms, sdst.host_ms, sdst.words, sdst.emits, sdst.table_ms,
                   sdst.checked ? "; every seed equal to the reference's own walk" : "");
+    if(shim_env("C4GPU_VERBOSE") && shim_env("C4GPU_SEED_FUSED") && atoi(shim_env("C4GPU_SEED_FUSED")))
+        g_message("c4gpu seed fused: %ld targets through c4gpu_seed_extend: %ld word hits, %ld extensions, %ld HSPs kept "
+                  "(%.0f ms with delivery)", sdst.fused_targets, sdst.fused_hits, sdst.fused_extended, sdst.fused_kept, sdst.fused_ms);
     return;
     }
