@@ -248,6 +248,34 @@ def _pairs(pairs):
     return arr, keep
 
 
+def _match_kind(match):
+    return {"dna2dna": _abi.MATCH_DNA2DNA, "protein2protein": _abi.MATCH_PROTEIN2PROTEIN,
+            "protein2dna": _abi.MATCH_PROTEIN2DNA}[match]
+
+
+def _hsp_seeds(seeds, chain=None, horizon0=None):
+    """The seed array and its length; with chains also their array, the horizon array and its length."""
+    n = len(seeds)
+    cs = (_abi.HspSeed * max(1, n))(*[_abi.HspSeed(*s) for s in seeds])
+    if chain is None:
+        return cs, n
+    nc = len(horizon0)
+    return cs, n, (C.c_int32 * max(1, n))(*chain), nc, (C.c_int32 * max(1, nc))(*horizon0)
+
+
+def _wordtab(ctx, width, wordlen, words):
+    """A word table (c4gpu_wordtab_create) of words = [(code, number of emissions)] in emission-list order."""
+    codes = (C.c_uint64 * max(1, len(words)))(*[c for c, _ in words])
+    first = [0]
+    for _, n in words:
+        first.append(first[-1] + n)
+    cf = (C.c_int32 * len(first))(*first)
+    tab = _lib().c4gpu_wordtab_create(ctx, width, wordlen, codes, cf, len(words))
+    if not tab:
+        raise _err("c4gpu_wordtab_create")
+    return tab
+
+
 def _viterbi_jobs(jobs):
     cj = (_abi.ViterbiJob * max(1, len(jobs)))()
     for i, j in enumerate(jobs):
@@ -394,12 +422,9 @@ class Engine:
         target_start) in one launch: [query_start, target_start, length, score, cobs] per seed.  `match`:
         "dna2dna" | "protein2protein" | "protein2dna"."""
         arr, keep = _pairs(pairs)
-        kind = {"dna2dna": _abi.MATCH_DNA2DNA, "protein2protein": _abi.MATCH_PROTEIN2PROTEIN,
-                "protein2dna": _abi.MATCH_PROTEIN2DNA}[match]
-        n = len(seeds)
-        cs = (_abi.HspSeed * max(1, n))(*[_abi.HspSeed(*s) for s in seeds])
+        cs, n = _hsp_seeds(seeds)
         out = (_abi.Hsp * max(1, n))()
-        if _lib().c4gpu_hsp_extend_batch(self.ctx, params, kind, arr, len(pairs), seedlen, dropoff, cs, n, out) != 0:
+        if _lib().c4gpu_hsp_extend_batch(self.ctx, params, _match_kind(match), arr, len(pairs), seedlen, dropoff, cs, n, out) != 0:
             raise _err("c4gpu_hsp_extend_batch")
         return [out[i].aslist() for i in range(n)]
 
@@ -407,14 +432,10 @@ class Engine:
         """The same with the diagonal horizon applied on the device (c4gpu_hsp_extend_chains): chain[k] names the horizon
         entry of seed k, horizon0[c] its value before the scan; a skipped seed comes back with length -1."""
         arr, keep = _pairs(pairs)
-        kind = {"dna2dna": _abi.MATCH_DNA2DNA, "protein2protein": _abi.MATCH_PROTEIN2PROTEIN,
-                "protein2dna": _abi.MATCH_PROTEIN2DNA}[match]
-        n, nc = len(seeds), len(horizon0)
-        cs = (_abi.HspSeed * max(1, n))(*[_abi.HspSeed(*s) for s in seeds])
-        cc = (C.c_int32 * max(1, n))(*chain)
-        h0 = (C.c_int32 * max(1, nc))(*horizon0)
+        cs, n, cc, nc, h0 = _hsp_seeds(seeds, chain, horizon0)
         out = (_abi.Hsp * max(1, n))()
-        if _lib().c4gpu_hsp_extend_chains(self.ctx, params, kind, arr, len(pairs), seedlen, dropoff, cs, n, cc, nc, h0, out) != 0:
+        if _lib().c4gpu_hsp_extend_chains(self.ctx, params, _match_kind(match), arr, len(pairs), seedlen, dropoff, cs, n, cc, nc, h0,
+                                          out) != 0:
             raise _err("c4gpu_hsp_extend_chains")
         return [out[i].aslist() for i in range(n)]
 
@@ -423,14 +444,11 @@ class Engine:
         ([query_start, target_start, length, score, cobs], dropped).  A dropped seed (below `threshold` after the extension
         that stops at masked positions) carries its masked-extended HSP."""
         arr, keep = _pairs(pairs)
-        kind = {"dna2dna": _abi.MATCH_DNA2DNA, "protein2protein": _abi.MATCH_PROTEIN2PROTEIN,
-                "protein2dna": _abi.MATCH_PROTEIN2DNA}[match]
-        n = len(seeds)
-        cs = (_abi.HspSeed * max(1, n))(*[_abi.HspSeed(*s) for s in seeds])
+        cs, n = _hsp_seeds(seeds)
         out = (_abi.Hsp * max(1, n))()
         dropped = (C.c_int32 * max(1, n))()
-        if _lib().c4gpu_hsp_extend_batch_masked(self.ctx, params, kind, arr, len(pairs), seedlen, dropoff, int(bool(mask_query)),
-                                                int(bool(mask_target)), threshold, cs, n, out, dropped) != 0:
+        if _lib().c4gpu_hsp_extend_batch_masked(self.ctx, params, _match_kind(match), arr, len(pairs), seedlen, dropoff,
+                                                int(bool(mask_query)), int(bool(mask_target)), threshold, cs, n, out, dropped) != 0:
             raise _err("c4gpu_hsp_extend_batch_masked")
         return [(out[i].aslist(), int(dropped[i])) for i in range(n)]
 
@@ -439,16 +457,12 @@ class Engine:
         """The same with the diagonal horizon applied on the device (c4gpu_hsp_extend_chains_masked): a skipped seed comes
         back with length -1 and dropped 0; a dropped seed moves its chain's horizon to its masked end."""
         arr, keep = _pairs(pairs)
-        kind = {"dna2dna": _abi.MATCH_DNA2DNA, "protein2protein": _abi.MATCH_PROTEIN2PROTEIN,
-                "protein2dna": _abi.MATCH_PROTEIN2DNA}[match]
-        n, nc = len(seeds), len(horizon0)
-        cs = (_abi.HspSeed * max(1, n))(*[_abi.HspSeed(*s) for s in seeds])
-        cc = (C.c_int32 * max(1, n))(*chain)
-        h0 = (C.c_int32 * max(1, nc))(*horizon0)
+        cs, n, cc, nc, h0 = _hsp_seeds(seeds, chain, horizon0)
         out = (_abi.Hsp * max(1, n))()
         dropped = (C.c_int32 * max(1, n))()
-        if _lib().c4gpu_hsp_extend_chains_masked(self.ctx, params, kind, arr, len(pairs), seedlen, dropoff, int(bool(mask_query)),
-                                                 int(bool(mask_target)), threshold, cs, n, cc, nc, h0, out, dropped) != 0:
+        if _lib().c4gpu_hsp_extend_chains_masked(self.ctx, params, _match_kind(match), arr, len(pairs), seedlen, dropoff,
+                                                 int(bool(mask_query)), int(bool(mask_target)), threshold, cs, n, cc, nc, h0, out,
+                                                 dropped) != 0:
             raise _err("c4gpu_hsp_extend_chains_masked")
         return [(out[i].aslist(), int(dropped[i])) for i in range(n)]
 
@@ -487,14 +501,7 @@ class Engine:
         order (the k-th word's emissions follow those of the words before it); symbols: bytes of automaton columns
         (0 = outside the alphabet).  Returns ([(position of the word's last symbol, emission index)], device ms)."""
         import numpy as np
-        codes = (C.c_uint64 * max(1, len(words)))(*[c for c, _ in words])
-        first = [0]
-        for _, n in words:
-            first.append(first[-1] + n)
-        cf = (C.c_int32 * len(first))(*first)
-        tab = _lib().c4gpu_wordtab_create(self.ctx, width, wordlen, codes, cf, len(words))
-        if not tab:
-            raise _err("c4gpu_wordtab_create")
+        tab = _wordtab(self.ctx, width, wordlen, words)
         try:
             n_hits = C.c_int64(0)
             cap = 1 << 16
@@ -520,16 +527,8 @@ class Engine:
         HSPs and one call only (more kept: an empty list, n_kept says how many); None: call again until they fit.
         first_hits: a list that receives, per pair, the walk index of its first word hit or -1 (c4gpu_seed_extend_first_hits)."""
         arr, keep = _pairs(pairs)
-        kind = {"dna2dna": _abi.MATCH_DNA2DNA, "protein2protein": _abi.MATCH_PROTEIN2PROTEIN,
-                "protein2dna": _abi.MATCH_PROTEIN2DNA}.get(match, match)
-        codes = (C.c_uint64 * max(1, len(words)))(*[c for c, _ in words])
-        first = [0]
-        for _, n in words:
-            first.append(first[-1] + n)
-        cf = (C.c_int32 * len(first))(*first)
-        tab = _lib().c4gpu_wordtab_create(self.ctx, width, wordlen, codes, cf, len(words))
-        if not tab:
-            raise _err("c4gpu_wordtab_create")
+        kind = match if isinstance(match, int) else _match_kind(match)
+        tab = _wordtab(self.ctx, width, wordlen, words)
         try:
             if emits is not None:
                 ce = (_abi.SeedEmit * max(1, len(emits)))(*[_abi.SeedEmit(p, q) for p, q in emits])

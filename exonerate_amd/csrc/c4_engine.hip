@@ -29,6 +29,7 @@
 #include "c4_pk16_bias.h"
 #include "c4_sdp_launch.h"
 #include "c4_sdp_host.h"
+#include "c4_hsp_extend.h"
 
 using namespace c4k;
 
@@ -81,4 +82,6 @@ namespace {
 #include "c4_engine_abi.inc"
 // ---- SDP on the device (seeded flavour): its own file, same translation unit ------------------------------------
 #include "c4_sdp_dev.inc"
+// ---- HSP seeding: the extension kernels and their entry points, then the word scan that feeds them ---------------
+#include "c4_hsp_dev.inc"
 #include "c4_seed_dev.inc"

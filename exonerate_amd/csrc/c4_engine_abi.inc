@@ -1,4 +1,4 @@
-// c4_engine_abi.inc -- part of c4_engine.hip (one translation unit; included there, in this order): the C ABI of include/c4gpu.h: contexts, batches, stages, raw Viterbi calls, HSP extension.
+// c4_engine_abi.inc -- part of c4_engine.hip (one translation unit; included there, in this order): the C ABI of include/c4gpu.h: contexts, batches, stages, raw Viterbi calls.
 // ---- the C ABI --------------------------------------------------------------------------------------------------
 struct c4gpu_batch {
     c4gpu_ctx *ctx;
@@ -219,205 +219,6 @@ int c4gpu_splice_predict(c4gpu_ctx *ctx, const c4gpu_params *params, const uint8
 }
 
 }  // extern "C"
-
-extern "C" int c4gpu_hsp_extend_batch(c4gpu_ctx *ctx, const c4gpu_params *params, int match_type, const c4gpu_pair *pairs,
-                                      int32_t n_pairs, int32_t seedlen, int32_t dropoff, const c4gpu_hsp_seed *seeds,
-                                      int32_t n_seeds, c4gpu_hsp *out);
-extern "C" int c4gpu_hsp_extend_chains(c4gpu_ctx *ctx, const c4gpu_params *params, int match_type, const c4gpu_pair *pairs,
-                                       int32_t n_pairs, int32_t seedlen, int32_t dropoff, const c4gpu_hsp_seed *seeds,
-                                       int32_t n_seeds, const int32_t *chain, int32_t n_chains, const int32_t *horizon0,
-                                       c4gpu_hsp *out) {
-    try {
-        if (hipSetDevice(ctx->device) != hipSuccess) return -1;
-        if (match_type < C4GPU_MATCH_DNA2DNA || match_type > C4GPU_MATCH_PROTEIN2DNA) { c4h::set_error("unknown match type"); return -1; }
-        if (!n_seeds) return 0;
-        const int aq = 1, at = match_type == C4GPU_MATCH_PROTEIN2DNA ? 3 : 1;
-        std::vector<int> first((size_t)n_chains + 1, 0), order((size_t)n_seeds);
-        for (int k = 0; k < n_seeds; k++) {
-            const c4gpu_hsp_seed &sd = seeds[k];
-            if (sd.pair < 0 || sd.pair >= n_pairs || sd.query_start < 0 || sd.target_start < 0 || chain[k] < 0 || chain[k] >= n_chains ||
-                sd.query_start + seedlen * aq > pairs[sd.pair].query_len || sd.target_start + seedlen * at > pairs[sd.pair].target_len) {
-                c4h::set_error("an HSP seed lies outside its pair or names no chain");
-                return -1;
-            }
-            first[chain[k] + 1]++;
-        }
-        for (int c = 0; c < n_chains; c++) first[c + 1] += first[c];
-        {
-            std::vector<int> fill(first.begin(), first.end() - 1);
-            for (int k = 0; k < n_seeds; k++) order[fill[chain[k]]++] = k;            // index order inside every chain
-        }
-        ResidentSeqs seqs;
-        if (seqs.build(ctx, match_type == C4GPU_MATCH_PROTEIN2DNA ? FAM_UNGAPPED_P2D : FAM_UNGAPPED, params, pairs, n_pairs)) return -1;
-        std::vector<HspJob> jobs(n_pairs);
-        for (int i = 0; i < n_pairs; i++) jobs[i] = HspJob{seqs.qoff[i], seqs.toff[i], seqs.qlen[i], seqs.tlen[i]};
-        DevBuf<HspJob> d_jobs;
-        DevBuf<c4gpu_hsp_seed> d_seeds;
-        DevBuf<c4gpu_hsp> d_out;
-        DevBuf<int> d_submat, d_order, d_first, d_h0;
-        const int32_t *mat = match_type == C4GPU_MATCH_DNA2DNA ? &params->dna_submat[0][0] : &params->protein_submat[0][0];
-        hipStream_t s = ctx->stream;
-        if (d_jobs.upload(jobs.data(), n_pairs, s) || d_seeds.upload(seeds, n_seeds, s) || d_out.alloc(n_seeds) ||
-            d_submat.upload(mat, 24 * 24, s) || d_order.upload(order.data(), n_seeds, s) ||
-            d_first.upload(first.data(), (size_t)n_chains + 1, s) || d_h0.upload(horizon0, n_chains, s)) return -1;
-        const int block = 64, grid = std::min((n_chains + block - 1) / block, 65535);
-        hipLaunchKernelGGL(hsp_chain_kernel, dim3(grid), dim3(block), 0, s, seqs.qcode.p, seqs.tcode.p, d_jobs.p, d_seeds.p, d_order.p,
-                           d_first.p, n_chains, d_h0.p, d_submat.p, aq, at, seedlen, dropoff, d_out.p);
-        HIP_OK(hipGetLastError());
-        if (d_out.download(out, n_seeds, s)) return -1;
-        HIP_OK(c4_stream_sync(s));
-        return 0;
-    } catch (const std::exception &e) {
-        c4h::set_error(std::string("c4gpu_hsp_extend_chains: ") + e.what());
-        return -1;
-    }
-}
-
-extern "C" int c4gpu_hsp_extend_batch(c4gpu_ctx *ctx, const c4gpu_params *params, int match_type, const c4gpu_pair *pairs,
-                                      int32_t n_pairs, int32_t seedlen, int32_t dropoff, const c4gpu_hsp_seed *seeds,
-                                      int32_t n_seeds, c4gpu_hsp *out) {
-    try {
-        if (hipSetDevice(ctx->device) != hipSuccess) return -1;
-        if (match_type < C4GPU_MATCH_DNA2DNA || match_type > C4GPU_MATCH_PROTEIN2DNA) { c4h::set_error("unknown match type"); return -1; }
-        if (!n_seeds) return 0;
-        const int aq = 1, at = match_type == C4GPU_MATCH_PROTEIN2DNA ? 3 : 1;
-        for (int k = 0; k < n_seeds; k++) {
-            const c4gpu_hsp_seed &sd = seeds[k];
-            if (sd.pair < 0 || sd.pair >= n_pairs || sd.query_start < 0 || sd.target_start < 0 ||
-                sd.query_start + seedlen * aq > pairs[sd.pair].query_len || sd.target_start + seedlen * at > pairs[sd.pair].target_len) {
-                c4h::set_error("an HSP seed lies outside its pair");
-                return -1;
-            }
-        }
-        // the coded arrays of a protein2dna batch are exactly what PROTEIN2DNA scoring reads (row of the codon at each
-        // target position); the 1:1 matches use the plain residue rows
-        ResidentSeqs seqs;
-        if (seqs.build(ctx, match_type == C4GPU_MATCH_PROTEIN2DNA ? FAM_UNGAPPED_P2D : FAM_UNGAPPED, params, pairs, n_pairs)) return -1;
-        std::vector<HspJob> jobs(n_pairs);
-        for (int i = 0; i < n_pairs; i++) jobs[i] = HspJob{seqs.qoff[i], seqs.toff[i], seqs.qlen[i], seqs.tlen[i]};
-        DevBuf<HspJob> d_jobs;
-        DevBuf<c4gpu_hsp_seed> d_seeds;
-        DevBuf<c4gpu_hsp> d_out;
-        DevBuf<int> d_submat;
-        const int32_t *mat = match_type == C4GPU_MATCH_DNA2DNA ? &params->dna_submat[0][0] : &params->protein_submat[0][0];
-        hipStream_t s = ctx->stream;
-        if (d_jobs.upload(jobs.data(), n_pairs, s) || d_seeds.upload(seeds, n_seeds, s) || d_out.alloc(n_seeds) ||
-            d_submat.upload(mat, 24 * 24, s)) return -1;
-        const int block = 64, grid = std::min((n_seeds + block - 1) / block, 65535);
-        hipLaunchKernelGGL(hsp_extend_kernel, dim3(grid), dim3(block), 0, s, seqs.qcode.p, seqs.tcode.p, d_jobs.p, d_seeds.p,
-                           n_seeds, d_submat.p, aq, at, seedlen, dropoff, d_out.p);
-        HIP_OK(hipGetLastError());
-        if (d_out.download(out, n_seeds, s)) return -1;
-        HIP_OK(c4_stream_sync(s));
-        return 0;
-    } catch (const std::exception &e) {
-        c4h::set_error(std::string("c4gpu_hsp_extend_batch: ") + e.what());
-        return -1;
-    }
-}
-
-// the two-stage extension of soft-masked sets (hspset.c:981-995), seed by seed (chain == nullptr) or chain by chain
-static int hsp_extend_masked(const char *who, c4gpu_ctx *ctx, const c4gpu_params *params, int match_type, const c4gpu_pair *pairs,
-                             int32_t n_pairs, int32_t seedlen, int32_t dropoff, int32_t mask_query, int32_t mask_target,
-                             int32_t threshold, const c4gpu_hsp_seed *seeds, int32_t n_seeds, const int32_t *chain, int32_t n_chains,
-                             const int32_t *horizon0, c4gpu_hsp *out, int32_t *dropped) {
-    try {
-        if (hipSetDevice(ctx->device) != hipSuccess) return -1;
-        if (match_type < C4GPU_MATCH_DNA2DNA || match_type > C4GPU_MATCH_PROTEIN2DNA) { c4h::set_error("unknown match type"); return -1; }
-        if (!n_seeds) return 0;
-        const int aq = 1, at = match_type == C4GPU_MATCH_PROTEIN2DNA ? 3 : 1;
-        std::vector<int> first, order;
-        if (chain) { first.assign((size_t)n_chains + 1, 0); order.resize((size_t)n_seeds); }
-        for (int k = 0; k < n_seeds; k++) {
-            const c4gpu_hsp_seed &sd = seeds[k];
-            if (sd.pair < 0 || sd.pair >= n_pairs || sd.query_start < 0 || sd.target_start < 0 ||
-                (chain && (chain[k] < 0 || chain[k] >= n_chains)) ||
-                sd.query_start + seedlen * aq > pairs[sd.pair].query_len || sd.target_start + seedlen * at > pairs[sd.pair].target_len) {
-                c4h::set_error("an HSP seed lies outside its pair or names no chain");
-                return -1;
-            }
-            if (chain) first[chain[k] + 1]++;
-        }
-        if (chain) {
-            for (int c = 0; c < n_chains; c++) first[c + 1] += first[c];
-            std::vector<int> fill(first.begin(), first.end() - 1);
-            for (int k = 0; k < n_seeds; k++) order[fill[chain[k]]++] = k;            // index order inside every chain
-        }
-        ResidentSeqs seqs;
-        if (seqs.build(ctx, match_type == C4GPU_MATCH_PROTEIN2DNA ? FAM_UNGAPPED_P2D : FAM_UNGAPPED, params, pairs, n_pairs)) return -1;
-        hipStream_t s = ctx->stream;
-        // the masks, from the raw residues the batch keeps (the coded arrays have lost the case): the 64 bytes of padding included
-        DevBuf<uint8_t> qmask, tmask;
-        const long long hq_n = seqs.total_q + 64, ht_n = seqs.total_t + 64;
-        if (mask_query) {
-            if (qmask.alloc((size_t)hq_n)) return -1;
-            hipLaunchKernelGGL(softmask_kernel, dim3(1024), dim3(256), 0, s, seqs.qraw.p, qmask.p, hq_n, aq,
-                               match_type == C4GPU_MATCH_DNA2DNA ? 'n' : 'x');
-        }
-        if (mask_target) {
-            if (tmask.alloc((size_t)ht_n)) return -1;
-            hipLaunchKernelGGL(softmask_kernel, dim3(1024), dim3(256), 0, s, seqs.traw.p, tmask.p, ht_n, at,
-                               match_type == C4GPU_MATCH_PROTEIN2PROTEIN ? 'x' : 'n');
-        }
-        HIP_OK(hipGetLastError());
-        std::vector<HspJob> jobs(n_pairs);
-        for (int i = 0; i < n_pairs; i++) jobs[i] = HspJob{seqs.qoff[i], seqs.toff[i], seqs.qlen[i], seqs.tlen[i]};
-        DevBuf<HspJob> d_jobs;
-        DevBuf<c4gpu_hsp_seed> d_seeds;
-        DevBuf<c4gpu_hsp> d_out;
-        DevBuf<int> d_submat, d_order, d_first, d_h0, d_dropped;
-        const int32_t *mat = match_type == C4GPU_MATCH_DNA2DNA ? &params->dna_submat[0][0] : &params->protein_submat[0][0];
-        if (d_jobs.upload(jobs.data(), n_pairs, s) || d_seeds.upload(seeds, n_seeds, s) || d_out.alloc(n_seeds) ||
-            d_dropped.alloc(n_seeds) || d_submat.upload(mat, 24 * 24, s)) return -1;
-        const int block = 64;
-        if (chain) {
-            if (d_order.upload(order.data(), n_seeds, s) || d_first.upload(first.data(), (size_t)n_chains + 1, s) ||
-                d_h0.upload(horizon0, n_chains, s)) return -1;
-            const int grid = std::min((n_chains + block - 1) / block, 65535);
-            hipLaunchKernelGGL(hsp_chain_masked_kernel, dim3(grid), dim3(block), 0, s, seqs.qcode.p, seqs.tcode.p, qmask.p, tmask.p,
-                               d_jobs.p, d_seeds.p, d_order.p, d_first.p, n_chains, d_h0.p, d_submat.p, aq, at, seedlen, dropoff,
-                               threshold, d_out.p, d_dropped.p);
-        } else {
-            const int grid = std::min((n_seeds + block - 1) / block, 65535);
-            hipLaunchKernelGGL(hsp_extend_masked_kernel, dim3(grid), dim3(block), 0, s, seqs.qcode.p, seqs.tcode.p, qmask.p, tmask.p,
-                               d_jobs.p, d_seeds.p, n_seeds, d_submat.p, aq, at, seedlen, dropoff, threshold, d_out.p, d_dropped.p);
-        }
-        HIP_OK(hipGetLastError());
-        if (d_out.download(out, n_seeds, s) || d_dropped.download(dropped, n_seeds, s)) return -1;
-        HIP_OK(c4_stream_sync(s));
-        return 0;
-    } catch (const std::exception &e) {
-        c4h::set_error(std::string(who) + ": " + e.what());
-        return -1;
-    }
-}
-
-extern "C" int c4gpu_hsp_extend_batch_masked(c4gpu_ctx *ctx, const c4gpu_params *params, int match_type, const c4gpu_pair *pairs,
-                                             int32_t n_pairs, int32_t seedlen, int32_t dropoff, int32_t mask_query,
-                                             int32_t mask_target, int32_t threshold, const c4gpu_hsp_seed *seeds, int32_t n_seeds,
-                                             c4gpu_hsp *out, int32_t *dropped) {
-    if (!mask_query && !mask_target) {           // nothing is ever masked (Alphabet_is_masked): the plain call, nothing dropped here
-        if (n_seeds > 0) memset(dropped, 0, sizeof(int32_t) * (size_t)n_seeds);
-        return c4gpu_hsp_extend_batch(ctx, params, match_type, pairs, n_pairs, seedlen, dropoff, seeds, n_seeds, out);
-    }
-    return hsp_extend_masked("c4gpu_hsp_extend_batch_masked", ctx, params, match_type, pairs, n_pairs, seedlen, dropoff, mask_query,
-                             mask_target, threshold, seeds, n_seeds, nullptr, 0, nullptr, out, dropped);
-}
-
-extern "C" int c4gpu_hsp_extend_chains_masked(c4gpu_ctx *ctx, const c4gpu_params *params, int match_type, const c4gpu_pair *pairs,
-                                              int32_t n_pairs, int32_t seedlen, int32_t dropoff, int32_t mask_query,
-                                              int32_t mask_target, int32_t threshold, const c4gpu_hsp_seed *seeds, int32_t n_seeds,
-                                              const int32_t *chain, int32_t n_chains, const int32_t *horizon0, c4gpu_hsp *out,
-                                              int32_t *dropped) {
-    if (!mask_query && !mask_target) {
-        if (n_seeds > 0) memset(dropped, 0, sizeof(int32_t) * (size_t)n_seeds);
-        return c4gpu_hsp_extend_chains(ctx, params, match_type, pairs, n_pairs, seedlen, dropoff, seeds, n_seeds, chain, n_chains,
-                                       horizon0, out);
-    }
-    if (!chain || !horizon0) { c4h::set_error("c4gpu_hsp_extend_chains_masked: no chains given"); return -1; }
-    return hsp_extend_masked("c4gpu_hsp_extend_chains_masked", ctx, params, match_type, pairs, n_pairs, seedlen, dropoff, mask_query,
-                             mask_target, threshold, seeds, n_seeds, chain, n_chains, horizon0, out, dropped);
-}
 
 static int viterbi_jobs(Engine &eng, const ResidentSeqs &seqs, int mode, const c4gpu_viterbi_job *jobs,
                         int32_t n_jobs, c4gpu_viterbi_result *results) {

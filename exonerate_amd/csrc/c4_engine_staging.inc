@@ -1,4 +1,4 @@
-// c4_engine_staging.inc -- part of c4_engine.hip (one translation unit; included there, in this order): what a batch needs before its first DP cell: model families, sequence preparation kernels (residue coding, codon tables, splice arrays), the HSP extension kernel, the device side of the reduced-space route, ResidentSeqs.
+// c4_engine_staging.inc -- part of c4_engine.hip (one translation unit; included there, in this order): what a batch needs before its first DP cell: model families, sequence preparation kernels (residue coding, codon tables, splice arrays), the device side of the reduced-space route, ResidentSeqs.
 // ---- which compiled family does a flattened model belong to? ----------------------------------------------
 template <class M>
 bool model_matches(const c4gpu_model &m) {
@@ -290,209 +290,6 @@ __global__ __launch_bounds__(256) void splice_tile_kernel(const uint8_t *__restr
                     out16[base + q] = o;
                 }
             }
-        }
-    }
-}
-
-// ---- HSP seeding: the ungapped X-drop extension of HSPset_seed_hsp (src/comparison/hspset.c:933-997) ----------------
-// One lane per seed: HSP_trim_ends (:837-870), HSP_init (:722-741), HSP_extend without masking (:743-812: left, then
-// right, best extension so far, stop below zero or `dropoff` under the best) and HSP_find_cobs (:426-441).  Residues
-// are read through the batch's coded arrays (qcode / tcode = substitution matrix rows; for PROTEIN2DNA tcode holds the
-// row of the codon starting at each position), the matrix sits in LDS.  Seeds of one diagonal neighbourhood read the
-// same cache lines; the work per seed is a few hundred bytes, so the kernel is latency- and not bandwidth-bound.
-struct HspJob { long long qoff, toff; int qlen, tlen; };
-__device__ __forceinline__ c4gpu_hsp hsp_extend_one(const uint8_t *__restrict__ qcode, const uint8_t *__restrict__ tcode, const HspJob jb,
-                                                     const c4gpu_hsp_seed sd, const int *sm, int aq, int at, int seedlen, int dropoff) {
-        const uint8_t *q = qcode + jb.qoff, *t = tcode + jb.toff;
-        auto sc = [&](int qp, int tp) { return sm[q[qp] * 24 + t[tp]]; };
-        int qs = sd.query_start, ts = sd.target_start, length = seedlen, i;
-        for (i = 0; i < length; i++) {                                   // HSP_trim_ends
-            if (sc(qs, ts) > 0) break;
-            qs += aq; ts += at;
-        }
-        length -= i;
-        int qp = qs + length * aq - aq, tp = ts + length * at - at;
-        while (length > 0) {
-            if (sc(qp, tp) > 0) break;
-            length--; qp -= aq; tp -= at;
-        }
-        int score = 0;                                                   // HSP_init
-        for (i = 0, qp = qs, tp = ts; i < length; i++, qp += aq, tp += at) score += sc(qp, tp);
-        int maxscore = score, extend, maxext;                            // HSP_extend: left
-        qp = qs - aq; tp = ts - at;
-        for (extend = 1, maxext = 0; qp >= 0 && tp >= 0; extend++) {
-            score += sc(qp, tp);
-            if (maxscore <= score) { maxscore = score; maxext = extend; }
-            else { if (score < 0) break; if (maxscore - score >= dropoff) break; }
-            qp -= aq; tp -= at;
-        }
-        qp = qs + length * aq; tp = ts + length * at;
-        qs -= maxext * aq; ts -= maxext * at; length += maxext;
-        score = maxscore;
-        for (extend = 1, maxext = 0; qp + aq <= jb.qlen && tp + at <= jb.tlen; extend++) {     // right
-            score += sc(qp, tp);
-            if (maxscore <= score) { maxscore = score; maxext = extend; }
-            else { if (score < 0) break; if (maxscore - score >= dropoff) break; }
-            qp += aq; tp += at;
-        }
-        length += maxext;
-        score = 0;                                                       // HSP_find_cobs
-        for (i = 0, qp = qs, tp = ts; i < length; i++, qp += aq, tp += at) {
-            score += sc(qp, tp);
-            if (score >= (maxscore >> 1)) break;
-        }
-        return c4gpu_hsp{qs, ts, length, maxscore, i};
-}
-
-__global__ void hsp_extend_kernel(const uint8_t *__restrict__ qcode, const uint8_t *__restrict__ tcode,
-                                  const HspJob *__restrict__ jobs, const c4gpu_hsp_seed *__restrict__ seeds, int n_seeds,
-                                  const int *__restrict__ submat, int aq, int at, int seedlen, int dropoff,
-                                  c4gpu_hsp *__restrict__ out) {
-    __shared__ int sm[24 * 24];
-    for (int x = threadIdx.x; x < 24 * 24; x += blockDim.x) sm[x] = submat[x];
-    __syncthreads();
-    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n_seeds; k += gridDim.x * blockDim.x)
-        out[k] = hsp_extend_one(qcode, tcode, jobs[seeds[k].pair], seeds[k], sm, aq, at, seedlen, dropoff);
-}
-
-// one lane per horizon chain (c4gpu_hsp_extend_chains): its seeds in order, skipped while below the running horizon
-__global__ void hsp_chain_kernel(const uint8_t *__restrict__ qcode, const uint8_t *__restrict__ tcode,
-                                 const HspJob *__restrict__ jobs, const c4gpu_hsp_seed *__restrict__ seeds,
-                                 const int *__restrict__ order, const int *__restrict__ chain_first, int n_chains,
-                                 const int *__restrict__ horizon0, const int *__restrict__ submat, int aq, int at, int seedlen,
-                                 int dropoff, c4gpu_hsp *__restrict__ out) {
-    __shared__ int sm[24 * 24];
-    for (int x = threadIdx.x; x < 24 * 24; x += blockDim.x) sm[x] = submat[x];
-    __syncthreads();
-    for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < n_chains; c += gridDim.x * blockDim.x) {
-        int horizon = horizon0[c];
-        for (int x = chain_first[c]; x < chain_first[c + 1]; x++) {
-            const int k = order[x];
-            if (seeds[k].target_start < horizon) { out[k] = c4gpu_hsp{0, 0, -1, 0, 0}; continue; }      // hspset.c:952-958
-            const c4gpu_hsp h = hsp_extend_one(qcode, tcode, jobs[seeds[k].pair], seeds[k], sm, aq, at, seedlen, dropoff);
-            out[k] = h;
-            horizon = h.target_start + h.length * at;                                                   // HSP_target_end, :990
-        }
-    }
-}
-
-// ---- soft-masked sequences: the two-stage extension of HSPset_seed_hsp (hspset.c:981-995) -----------------------------
-// Per position of the raw residues, is the strand position starting there masked (match.c:156-158,178-182,212-220)?  A
-// symbol is masked when the alphabet's SOFTMASK filter maps it elsewhere than TO_UPPER does (alphabet.h:87,
-// alphabet.c:124-129): every lower-case letter but the wildcard itself (`wild`: 'n' for DNA, 'x' for protein).  A strand of
-// advance 3 ORs its three bases; the last two positions of a sequence start no codon and are never read.  The coded arrays
-// fold case away (Submat index), so this reads the raw bytes; built only for a side whose alphabet is soft-masked.
-__global__ void softmask_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, long long n, int advance, int wild) {
-    for (long long x = blockIdx.x * (long long)blockDim.x + threadIdx.x; x < n; x += (long long)gridDim.x * blockDim.x) {
-        int m = 0;
-        for (int d = 0; d < advance; d++)
-            if (x + d < n) { const int c = in[x + d]; m |= (c >= 'a' && c <= 'z' && c != wild) ? 1 : 0; }
-        out[x] = (uint8_t)m;
-    }
-}
-
-// One seed: trim and initial score as above; HSP_extend stopping in front of the first masked position (hspset.c:762-765,
-// 794-797); below `threshold` the seed is DROPPED (*dropped = 1, the HSP returned is the masked-extended one: the caller
-// forms HSP_target_end from it, :985-989); otherwise HSP_extend again from the grown ends without the mask test (its left
-// pass starts from the first stage's score, after that stage has gone right already: not one plain extension).
-// qmask / tmask: null for a side that is not soft-masked.
-__device__ __forceinline__ c4gpu_hsp hsp_extend_one_masked(const uint8_t *__restrict__ qcode, const uint8_t *__restrict__ tcode,
-                                                            const uint8_t *__restrict__ qmask, const uint8_t *__restrict__ tmask,
-                                                            const HspJob jb, const c4gpu_hsp_seed sd, const int *sm, int aq, int at,
-                                                            int seedlen, int dropoff, int threshold, int *dropped) {
-        const uint8_t *q = qcode + jb.qoff, *t = tcode + jb.toff;
-        const uint8_t *qm = qmask ? qmask + jb.qoff : nullptr, *tm = tmask ? tmask + jb.toff : nullptr;
-        auto sc = [&](int qp, int tp) { return sm[q[qp] * 24 + t[tp]]; };
-        auto masked = [&](int qp, int tp) { return (qm && qm[qp]) || (tm && tm[tp]); };
-        int qs = sd.query_start, ts = sd.target_start, length = seedlen, i;
-        for (i = 0; i < length; i++) {                                   // HSP_trim_ends
-            if (sc(qs, ts) > 0) break;
-            qs += aq; ts += at;
-        }
-        length -= i;
-        int qp = qs + length * aq - aq, tp = ts + length * at - at;
-        while (length > 0) {
-            if (sc(qp, tp) > 0) break;
-            length--; qp -= aq; tp -= at;
-        }
-        int score = 0;                                                   // HSP_init
-        for (i = 0, qp = qs, tp = ts; i < length; i++, qp += aq, tp += at) score += sc(qp, tp);
-        int maxscore = score;
-        *dropped = 0;
-        for (int stage = 0; stage < 2; stage++) {                        // HSP_extend(forbid_masked = TRUE), then (FALSE)
-            const bool forbid = stage == 0;
-            int extend, maxext;
-            score = maxscore;
-            qp = qs - aq; tp = ts - at;
-            for (extend = 1, maxext = 0; qp >= 0 && tp >= 0; extend++) {                            // left
-                if (forbid && masked(qp, tp)) break;
-                score += sc(qp, tp);
-                if (maxscore <= score) { maxscore = score; maxext = extend; }
-                else { if (score < 0) break; if (maxscore - score >= dropoff) break; }
-                qp -= aq; tp -= at;
-            }
-            qp = qs + length * aq; tp = ts + length * at;
-            qs -= maxext * aq; ts -= maxext * at; length += maxext;
-            score = maxscore;
-            for (extend = 1, maxext = 0; qp + aq <= jb.qlen && tp + at <= jb.tlen; extend++) {      // right
-                if (forbid && masked(qp, tp)) break;
-                score += sc(qp, tp);
-                if (maxscore <= score) { maxscore = score; maxext = extend; }
-                else { if (score < 0) break; if (maxscore - score >= dropoff) break; }
-                qp += aq; tp += at;
-            }
-            length += maxext;
-            if (forbid && maxscore < threshold) {                        // hspset.c:985-989
-                *dropped = 1;
-                return c4gpu_hsp{qs, ts, length, maxscore, 0};
-            }
-        }
-        score = 0;                                                       // HSP_find_cobs
-        for (i = 0, qp = qs, tp = ts; i < length; i++, qp += aq, tp += at) {
-            score += sc(qp, tp);
-            if (score >= (maxscore >> 1)) break;
-        }
-        return c4gpu_hsp{qs, ts, length, maxscore, i};
-}
-
-__global__ void hsp_extend_masked_kernel(const uint8_t *__restrict__ qcode, const uint8_t *__restrict__ tcode,
-                                         const uint8_t *__restrict__ qmask, const uint8_t *__restrict__ tmask,
-                                         const HspJob *__restrict__ jobs, const c4gpu_hsp_seed *__restrict__ seeds, int n_seeds,
-                                         const int *__restrict__ submat, int aq, int at, int seedlen, int dropoff, int threshold,
-                                         c4gpu_hsp *__restrict__ out, int *__restrict__ dropped) {
-    __shared__ int sm[24 * 24];
-    for (int x = threadIdx.x; x < 24 * 24; x += blockDim.x) sm[x] = submat[x];
-    __syncthreads();
-    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n_seeds; k += gridDim.x * blockDim.x) {
-        int d;
-        out[k] = hsp_extend_one_masked(qcode, tcode, qmask, tmask, jobs[seeds[k].pair], seeds[k], sm, aq, at, seedlen, dropoff,
-                                       threshold, &d);
-        dropped[k] = d;
-    }
-}
-
-// the chain form: a dropped seed moves the running horizon to its masked end, a kept one to the stored HSP's target end
-// (hspset.c:985-995, seed by seed)
-__global__ void hsp_chain_masked_kernel(const uint8_t *__restrict__ qcode, const uint8_t *__restrict__ tcode,
-                                        const uint8_t *__restrict__ qmask, const uint8_t *__restrict__ tmask,
-                                        const HspJob *__restrict__ jobs, const c4gpu_hsp_seed *__restrict__ seeds,
-                                        const int *__restrict__ order, const int *__restrict__ chain_first, int n_chains,
-                                        const int *__restrict__ horizon0, const int *__restrict__ submat, int aq, int at, int seedlen,
-                                        int dropoff, int threshold, c4gpu_hsp *__restrict__ out, int *__restrict__ dropped) {
-    __shared__ int sm[24 * 24];
-    for (int x = threadIdx.x; x < 24 * 24; x += blockDim.x) sm[x] = submat[x];
-    __syncthreads();
-    for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < n_chains; c += gridDim.x * blockDim.x) {
-        int horizon = horizon0[c];
-        for (int x = chain_first[c]; x < chain_first[c + 1]; x++) {
-            const int k = order[x];
-            if (seeds[k].target_start < horizon) { out[k] = c4gpu_hsp{0, 0, -1, 0, 0}; dropped[k] = 0; continue; }
-            int d;
-            const c4gpu_hsp h = hsp_extend_one_masked(qcode, tcode, qmask, tmask, jobs[seeds[k].pair], seeds[k], sm, aq, at, seedlen,
-                                                      dropoff, threshold, &d);
-            out[k] = h;
-            dropped[k] = d;
-            horizon = h.target_start + h.length * at;
         }
     }
 }

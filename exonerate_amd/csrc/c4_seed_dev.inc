@@ -16,9 +16,36 @@ namespace {
 
 struct WordSlot { unsigned long long code; int first, count; };
 
-__device__ __forceinline__ unsigned long long word_hash(unsigned long long c) {
+__host__ __device__ __forceinline__ unsigned long long word_hash(unsigned long long c) {
     c ^= c >> 31; c *= 0x9E3779B97F4A7C15ull; c ^= c >> 29;
     return c;
+}
+
+// The kernels below that scan or reduce run 256 threads with 8 items each; part: 256 entries of LDS.
+constexpr int SEED_ITEMS = 8;
+
+// the sum over the block (in thread 0 only)
+template <class T> __device__ __forceinline__ T block_sum(T mine, T *part) {
+    part[threadIdx.x] = mine;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
+        __syncthreads();
+    }
+    return part[0];
+}
+
+// the sum over the threads in front of this one (Hillis-Steele)
+template <class T> __device__ __forceinline__ T block_exclusive_scan(T mine, T *part) {
+    part[threadIdx.x] = mine;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+        const T add = (int)threadIdx.x >= off ? part[threadIdx.x - off] : 0;
+        __syncthreads();
+        part[threadIdx.x] += add;
+        __syncthreads();
+    }
+    return part[threadIdx.x] - mine;
 }
 
 // cnt[i] = emissions of the word whose last symbol is symbols[i] (0: no word ends there); blocksum[b] = their sum per block
@@ -27,10 +54,9 @@ __global__ __launch_bounds__(256) void seed_count_kernel(const uint8_t *__restri
                                                          int *__restrict__ cnt, int *__restrict__ first,
                                                          unsigned long long *__restrict__ blocksum) {
     __shared__ unsigned long long part[256];
-    const int items = 8;
-    const long long base = ((long long)blockIdx.x * 256 + threadIdx.x) * items;
+    const long long base = ((long long)blockIdx.x * 256 + threadIdx.x) * SEED_ITEMS;
     unsigned long long mine = 0;
-    for (int k = 0; k < items; k++) {
+    for (int k = 0; k < SEED_ITEMS; k++) {
         const long long i = base + k;
         if (i >= n) break;
         int c = 0, f = 0;
@@ -55,13 +81,8 @@ __global__ __launch_bounds__(256) void seed_count_kernel(const uint8_t *__restri
         cnt[i] = c; first[i] = f;
         mine += (unsigned)c;
     }
-    part[threadIdx.x] = mine;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) blocksum[blockIdx.x] = part[0];
+    const unsigned long long sum = block_sum(mine, part);
+    if (threadIdx.x == 0) blocksum[blockIdx.x] = sum;
 }
 
 // exclusive prefix sum of the block sums, one workgroup
@@ -89,31 +110,31 @@ __global__ __launch_bounds__(1024) void seed_blockscan_kernel(unsigned long long
     if (threadIdx.x == 0) *total = carry;
 }
 
-// every hit to its place: block offset + the prefix inside the block
-__global__ __launch_bounds__(256) void seed_fill_kernel(int n, const int *__restrict__ cnt, const int *__restrict__ first,
-                                                        const unsigned long long *__restrict__ blockoff,
-                                                        c4gpu_word_hit *__restrict__ hits, unsigned long long cap) {
+// A thread's positions and their hits, every hit with its place: hit_base + block offset + the prefix inside the block.
+// emit(position, emission, place)
+template <class Emit>
+__device__ __forceinline__ void seed_walk_hits(int n, const int *__restrict__ cnt, const int *__restrict__ first,
+                                               unsigned long long hit_base, Emit emit) {
     __shared__ unsigned long long part[256];
-    const int items = 8;
-    const long long base = ((long long)blockIdx.x * 256 + threadIdx.x) * items;
+    const long long base = ((long long)blockIdx.x * 256 + threadIdx.x) * SEED_ITEMS;
     unsigned long long mine = 0;
-    for (int k = 0; k < items; k++) if (base + k < n) mine += (unsigned)cnt[base + k];
-    part[threadIdx.x] = mine;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        const unsigned long long add = (int)threadIdx.x >= off ? part[threadIdx.x - off] : 0;
-        __syncthreads();
-        part[threadIdx.x] += add;
-        __syncthreads();
-    }
-    unsigned long long pos = blockoff[blockIdx.x] + part[threadIdx.x] - mine;
-    for (int k = 0; k < items; k++) {
+    for (int k = 0; k < SEED_ITEMS; k++) if (base + k < n) mine += (unsigned)cnt[base + k];
+    unsigned long long pos = hit_base + block_exclusive_scan(mine, part);
+    for (int k = 0; k < SEED_ITEMS; k++) {
         const long long i = base + k;
         if (i >= n) break;
         const int c = cnt[i], f = first[i];
-        for (int e = 0; e < c; e++, pos++)
-            if (pos < cap) hits[pos] = c4gpu_word_hit{(int32_t)i, f + e};
+        for (int e = 0; e < c; e++, pos++) emit((int)i, f + e, pos);
     }
+}
+
+// the hit list of c4gpu_seed_scan
+__global__ __launch_bounds__(256) void seed_fill_kernel(int n, const int *__restrict__ cnt, const int *__restrict__ first,
+                                                        const unsigned long long *__restrict__ blockoff,
+                                                        c4gpu_word_hit *__restrict__ hits, unsigned long long cap) {
+    seed_walk_hits(n, cnt, first, blockoff[blockIdx.x], [&](int i, int emission, unsigned long long pos) {
+        if (pos < cap) hits[pos] = c4gpu_word_hit{i, emission};
+    });
 }
 
 // ---- c4gpu_seed_extend: the hits stay here and become the HSPs a fresh HSPset per pair would store ---------------------
@@ -121,10 +142,10 @@ __global__ __launch_bounds__(256) void seed_fill_kernel(int n, const int *__rest
 // order only through the horizon entry the seed is tested against (:939-958) and moves (:990).  So: every hit becomes a seed
 // with the number of its entry (its slot: all entries of all pairs numbered through, slot_base[pair] + section * at + tf, or
 // n_slots for a seed without one); a stable radix sort groups the walk indices by slot, walk order kept inside a slot; one
-// lane per run of equal slots replays that entry alone (running horizon, hsp_extend_one); a prefix sum over the kept
+// lane per run of equal slots replays that entry alone (hsp_horizon_step, c4_hsp_extend.h); a prefix sum over the kept
 // verdicts in walk-index order lays the kept HSPs out as HSP_store met them.
 
-// seed_fill_kernel with the seed and its slot in place of the hit
+// the same walk with the seed and its slot in place of the hit
 __global__ __launch_bounds__(256) void seed_expand_kernel(int n, const int *__restrict__ cnt, const int *__restrict__ first,
                                                           const unsigned long long *__restrict__ blockoff, unsigned long long hit_base,
                                                           unsigned long long n_hits, const c4gpu_seed_emit *__restrict__ emits,
@@ -133,45 +154,26 @@ __global__ __launch_bounds__(256) void seed_expand_kernel(int n, const int *__re
                                                           c4gpu_hsp_seed *__restrict__ seeds, unsigned *__restrict__ keys,
                                                           int *__restrict__ vals, unsigned long long *__restrict__ outside,
                                                           unsigned long long *__restrict__ first_hit) {
-    __shared__ unsigned long long part[256];
-    const int items = 8;
-    const long long base = ((long long)blockIdx.x * 256 + threadIdx.x) * items;
-    unsigned long long mine = 0;
-    for (int k = 0; k < items; k++) if (base + k < n) mine += (unsigned)cnt[base + k];
-    part[threadIdx.x] = mine;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        const unsigned long long add = (int)threadIdx.x >= off ? part[threadIdx.x - off] : 0;
-        __syncthreads();
-        part[threadIdx.x] += add;
-        __syncthreads();
-    }
-    unsigned long long pos = hit_base + blockoff[blockIdx.x] + part[threadIdx.x] - mine;
-    for (int k = 0; k < items; k++) {
-        const long long i = base + k;
-        if (i >= n) break;
-        const int c = cnt[i], f = first[i];
-        const int ts = (int)i * scale + offset - modifier;
-        for (int e = 0; e < c; e++, pos++) {
-            if (pos >= n_hits) continue;
-            const c4gpu_seed_emit em = emits[f + e];
-            const HspJob jb = jobs[em.pair];
-            if (pos < first_hit[em.pair]) atomicMin(&first_hit[em.pair], pos);      // (it only ever falls: a stale read is too large)
-            unsigned key = n_slots;
-            int pair = em.pair;
-            if (ts < 0 || jb.qlen <= 0 || em.query_pos + seedlen > jb.qlen || (long long)ts + (long long)seedlen * at > jb.tlen) {
-                *outside = 1;                                            // the call fails; the seed is never read through
-                pair = -1;
-            } else {
-                const int diag = ts - em.query_pos * at;                 // hspset.c:941-944 (query advance 1)
-                const int section = (diag + jb.qlen) % jb.qlen;          // C's remainder: negative above the main diagonal's reach
-                if (section >= 0) key = slot_base[em.pair] + (unsigned)section * (unsigned)at + (unsigned)(ts % at);
-            }
-            seeds[pos] = c4gpu_hsp_seed{pair, em.query_pos, ts};
-            keys[pos] = key;
-            vals[pos] = (int)pos;
+    seed_walk_hits(n, cnt, first, hit_base + blockoff[blockIdx.x], [&](int i, int emission, unsigned long long pos) {
+        if (pos >= n_hits) return;
+        const int ts = i * scale + offset - modifier;
+        const c4gpu_seed_emit em = emits[emission];
+        const HspJob jb = jobs[em.pair];
+        if (pos < first_hit[em.pair]) atomicMin(&first_hit[em.pair], pos);      // (it only ever falls: a stale read is too large)
+        unsigned key = n_slots;
+        int pair = em.pair;
+        if (ts < 0 || jb.qlen <= 0 || em.query_pos + seedlen > jb.qlen || (long long)ts + (long long)seedlen * at > jb.tlen) {
+            *outside = 1;                                            // the call fails; the seed is never read through
+            pair = -1;
+        } else {
+            const int diag = ts - em.query_pos * at;                 // hspset.c:941-944 (query advance 1)
+            const int section = (diag + jb.qlen) % jb.qlen;          // C's remainder: negative above the main diagonal's reach
+            if (section >= 0) key = slot_base[em.pair] + (unsigned)section * (unsigned)at + (unsigned)(ts % at);
         }
-    }
+        seeds[pos] = c4gpu_hsp_seed{pair, em.query_pos, ts};
+        keys[pos] = key;
+        vals[pos] = (int)pos;
+    });
 }
 
 // LSD radix sort, 8 bits a pass, one wave per tile of 2048: digit histogram (hist[digit * n_blocks + block], so that one
@@ -222,28 +224,24 @@ __global__ __launch_bounds__(64) void seed_sort_scatter_kernel(const unsigned *_
 
 // One lane per run of equal slots in the sorted list (a seed without a horizon entry is a run of its own): HSPset_seed_hsp
 // seed by seed on that entry alone.  verdict[k] of walk index k: 0 skipped, 1 extended and below the threshold, 2 kept.
-__global__ void seed_chain_kernel(const uint8_t *__restrict__ qcode, const uint8_t *__restrict__ tcode, const HspJob *__restrict__ jobs,
-                                  const c4gpu_hsp_seed *__restrict__ seeds, const unsigned *__restrict__ keys,
-                                  const int *__restrict__ order, long long n, unsigned n_slots, const int *__restrict__ submat, int aq,
-                                  int at, int seedlen, int dropoff, int threshold, uint8_t *__restrict__ verdict,
-                                  c4gpu_hsp *__restrict__ hsps) {
+__global__ void seed_chain_kernel(const HspArgs a, const c4gpu_hsp_seed *__restrict__ seeds, const unsigned *__restrict__ keys,
+                                  const int *__restrict__ order, long long n, unsigned n_slots, const int *__restrict__ submat,
+                                  uint8_t *__restrict__ verdict, c4gpu_hsp *__restrict__ hsps) {
     __shared__ int sm[24 * 24];
-    for (int x = threadIdx.x; x < 24 * 24; x += blockDim.x) sm[x] = submat[x];
-    __syncthreads();
+    hsp_load_matrix(sm, submat);
     for (long long x = blockIdx.x * (long long)blockDim.x + threadIdx.x; x < n; x += (long long)gridDim.x * blockDim.x) {
         const unsigned key = keys[x];
         const bool entry = key != n_slots;
         if (entry && x > 0 && keys[x - 1] == key) continue;              // not the first of its run
-        int horizon = 0;                                                 // a fresh set's entries start at 0
-        for (long long y = x; y < n && keys[y] == key; y++) {
+        int horizon = 0;                                                 // a fresh set's entries start at 0: no seed (their
+        for (long long y = x; y < n && keys[y] == key; y++) {            // target_start >= 0) lies below, with an entry or not
             const int k = order[y];
             const c4gpu_hsp_seed sd = seeds[k];
-            if (sd.pair < 0 || (entry && sd.target_start < horizon)) verdict[k] = 0;                     // hspset.c:952-958
+            c4gpu_hsp h;
+            if (sd.pair < 0 || !hsp_horizon_step<false>(a, sm, sd, horizon, &h, nullptr)) verdict[k] = 0;
             else {
-                const c4gpu_hsp h = hsp_extend_one(qcode, tcode, jobs[sd.pair], sd, sm, aq, at, seedlen, dropoff);
                 hsps[k] = h;
-                verdict[k] = h.score >= threshold ? 2 : 1;               // HSP_store
-                horizon = h.target_start + h.length * at;                // HSP_target_end, :990 (stored or not)
+                verdict[k] = h.score >= a.threshold ? 2 : 1;             // HSP_store
             }
             if (!entry) break;
         }
@@ -255,20 +253,14 @@ __global__ __launch_bounds__(256) void seed_verdict_count_kernel(const uint8_t *
                                                                  unsigned long long *__restrict__ blocksum,
                                                                  unsigned long long *__restrict__ n_below) {
     __shared__ unsigned kept[256], under[256];
-    const int items = 8;
-    const long long base = ((long long)blockIdx.x * 256 + threadIdx.x) * items;
+    const long long base = ((long long)blockIdx.x * 256 + threadIdx.x) * SEED_ITEMS;
     unsigned a = 0, b = 0;
-    for (int k = 0; k < items; k++)
+    for (int k = 0; k < SEED_ITEMS; k++)
         if (base + k < n) { const int v = verdict[base + k]; a += v == 2; b += v == 1; }
-    kept[threadIdx.x] = a; under[threadIdx.x] = b;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) { kept[threadIdx.x] += kept[threadIdx.x + off]; under[threadIdx.x] += under[threadIdx.x + off]; }
-        __syncthreads();
-    }
+    a = block_sum(a, kept); b = block_sum(b, under);
     if (threadIdx.x == 0) {
-        blocksum[blockIdx.x] = kept[0];
-        if (under[0]) atomicAdd(n_below, (unsigned long long)under[0]);
+        blocksum[blockIdx.x] = a;
+        if (b) atomicAdd(n_below, (unsigned long long)b);
     }
 }
 
@@ -278,20 +270,11 @@ __global__ __launch_bounds__(256) void seed_compact_kernel(const uint8_t *__rest
                                                            const c4gpu_hsp_seed *__restrict__ seeds, const c4gpu_hsp *__restrict__ hsps,
                                                            c4gpu_seed_hsp *__restrict__ out, unsigned long long cap) {
     __shared__ unsigned part[256];
-    const int items = 8;
-    const long long base = ((long long)blockIdx.x * 256 + threadIdx.x) * items;
+    const long long base = ((long long)blockIdx.x * 256 + threadIdx.x) * SEED_ITEMS;
     unsigned mine = 0;
-    for (int k = 0; k < items; k++) if (base + k < n) mine += verdict[base + k] == 2;
-    part[threadIdx.x] = mine;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        const unsigned add = (int)threadIdx.x >= off ? part[threadIdx.x - off] : 0;
-        __syncthreads();
-        part[threadIdx.x] += add;
-        __syncthreads();
-    }
-    unsigned long long pos = blockoff[blockIdx.x] + part[threadIdx.x] - mine;
-    for (int k = 0; k < items; k++) {
+    for (int k = 0; k < SEED_ITEMS; k++) if (base + k < n) mine += verdict[base + k] == 2;
+    unsigned long long pos = blockoff[blockIdx.x] + block_exclusive_scan(mine, part);
+    for (int k = 0; k < SEED_ITEMS; k++) {
         const long long i = base + k;
         if (i >= n) break;
         if (verdict[i] != 2) continue;
@@ -349,9 +332,7 @@ extern "C" c4gpu_wordtab *c4gpu_wordtab_create(c4gpu_ctx *ctx, int32_t width, in
         for (int k = 0; k < n_words; k++) {
             const int count = emit_first[k + 1] - emit_first[k];
             if (count <= 0) continue;                                   // a word without emissions reports nothing
-            unsigned long long c = codes[k];
-            c ^= c >> 31; c *= 0x9E3779B97F4A7C15ull; c ^= c >> 29;
-            unsigned h = (unsigned)c & t->mask;
+            unsigned h = (unsigned)word_hash(codes[k]) & t->mask;
             while (host[h].count) {
                 if (host[h].code == codes[k]) { c4h::set_error("word table: a word listed twice"); return nullptr; }
                 h = (h + 1) & t->mask;
@@ -369,13 +350,23 @@ extern "C" c4gpu_wordtab *c4gpu_wordtab_create(c4gpu_ctx *ctx, int32_t width, in
 
 extern "C" void c4gpu_wordtab_destroy(c4gpu_wordtab *t) { delete t; }
 
+// The count stage over the n symbols at d_sym + sym_off: emissions and first emission per position (d_cnt, d_first, same
+// offset), the exclusive prefix of the per-block sums at d_blocksum + blk_off and their total in d_total[total_at].
+static int seed_count_blocks(long long n) { return (int)((n + 256 * SEED_ITEMS - 1) / (256 * SEED_ITEMS)); }
+static void seed_count_launch(c4gpu_wordtab *t, hipStream_t s, size_t sym_off, int n, size_t blk_off, size_t total_at) {
+    const int n_blocks = seed_count_blocks(n);
+    hipLaunchKernelGGL(seed_count_kernel, dim3(n_blocks), dim3(256), 0, s, t->d_sym.p + sym_off, n, t->width, t->wordlen, t->slots.p,
+                       t->mask, t->d_cnt.p + sym_off, t->d_first.p + sym_off, t->d_blocksum.p + blk_off);
+    hipLaunchKernelGGL(seed_blockscan_kernel, dim3(1), dim3(1024), 0, s, t->d_blocksum.p + blk_off, n_blocks, t->d_total.p + total_at);
+}
+
 extern "C" int c4gpu_seed_scan(c4gpu_ctx *ctx, c4gpu_wordtab *t, const uint8_t *symbols, int32_t n, c4gpu_word_hit *hits,
                                int64_t cap, int64_t *n_hits) {
     if (hipSetDevice(ctx->device) != hipSuccess) { c4h::set_error("hipSetDevice failed"); return -1; }
     *n_hits = 0;
     if (n <= 0) return 0;
     hipStream_t s = ctx->stream;
-    const int per_block = 256 * 8, n_blocks = (n + per_block - 1) / per_block;
+    const int n_blocks = seed_count_blocks(n);
     // C4GPU_TRACE: where a scan's wall time goes, call by call (a scan beside another thread's long kernel: r05)
     const bool laps_on = c4cfg::has(c4cfg::TRACE);
     auto lap_t = std::chrono::steady_clock::now();
@@ -393,9 +384,7 @@ extern "C" int c4gpu_seed_scan(c4gpu_ctx *ctx, c4gpu_wordtab *t, const uint8_t *
         t->d_total.alloc(1) || t->d_hits.alloc((size_t)std::max<int64_t>(cap, 1))) return -1;
     lap("allocs");
     HIP_OK(hipEventRecord(ctx->ev0, s));
-    hipLaunchKernelGGL(seed_count_kernel, dim3(n_blocks), dim3(256), 0, s, t->d_sym.p, n, t->width, t->wordlen, t->slots.p, t->mask,
-                       t->d_cnt.p, t->d_first.p, t->d_blocksum.p);
-    hipLaunchKernelGGL(seed_blockscan_kernel, dim3(1), dim3(1024), 0, s, t->d_blocksum.p, n_blocks, t->d_total.p);
+    seed_count_launch(t, s, 0, n, 0, 0);
     hipLaunchKernelGGL(seed_fill_kernel, dim3(n_blocks), dim3(256), 0, s, n, t->d_cnt.p, t->d_first.p, t->d_blocksum.p, t->d_hits.p,
                        (unsigned long long)std::max<int64_t>(cap, 0));
     HIP_OK(hipGetLastError());
@@ -464,7 +453,7 @@ extern "C" int c4gpu_seed_extend(c4gpu_ctx *ctx, c4gpu_wordtab *t, const c4gpu_p
                 c4h::set_error("c4gpu_seed_extend: the pairs do not all name one target buffer and length");
                 return -1;
             }
-        const int aq = 1, at = match_type == C4GPU_MATCH_PROTEIN2DNA ? 3 : 1;
+        const int aq = 1, at = hsp_target_advance(match_type);
         long long n_slots = 0;
         std::vector<unsigned> slot_base((size_t)std::max(1, n_pairs));
         for (int i = 0; i < n_pairs; i++) {
@@ -473,37 +462,29 @@ extern "C" int c4gpu_seed_extend(c4gpu_ctx *ctx, c4gpu_wordtab *t, const c4gpu_p
             if (n_slots > 0x7fffffffLL) { c4h::set_error("c4gpu_seed_extend: more than 2^31 - 1 horizon entries"); return -1; }
         }
         // the strings behind each other in one buffer, each with whole count blocks of its own
-        const int per_block = 256 * 8;
         std::vector<size_t> sym_off((size_t)n_strings + 1, 0), blk_off((size_t)n_strings + 1, 0);
         for (int s = 0; s < n_strings; s++) {
-            const size_t n = (size_t)std::max(0, n_symbols[s]);
-            sym_off[s + 1] = sym_off[s] + n;
-            blk_off[s + 1] = blk_off[s] + (n + per_block - 1) / per_block;
+            const int n = std::max(0, n_symbols[s]);
+            sym_off[s + 1] = sym_off[s] + (size_t)n;
+            blk_off[s + 1] = blk_off[s] + (size_t)seed_count_blocks(n);
         }
         const size_t total_sym = sym_off[n_strings];
         t->first_hit_pairs = n_pairs; t->first_hit_any = false;
         if (!total_sym || !n_pairs || !t->n_emissions) return 0;
         ResidentSeqs seqs;
-        if (seqs.build(ctx, match_type == C4GPU_MATCH_PROTEIN2DNA ? FAM_UNGAPPED_P2D : FAM_UNGAPPED, params, pairs, n_pairs)) return -1;
-        std::vector<HspJob> jobs(n_pairs);
-        for (int i = 0; i < n_pairs; i++) jobs[i] = HspJob{seqs.qoff[i], seqs.toff[i], seqs.qlen[i], seqs.tlen[i]};
-        const int32_t *mat = match_type == C4GPU_MATCH_DNA2DNA ? &params->dna_submat[0][0] : &params->protein_submat[0][0];
+        if (seqs.build(ctx, hsp_family(match_type), params, pairs, n_pairs)) return -1;
+        const std::vector<HspJob> jobs = hsp_jobs(seqs, n_pairs);
         hipStream_t s = ctx->stream;
         std::vector<unsigned long long> totals((size_t)n_strings, 0), hit_base((size_t)n_strings + 1, 0);
         std::vector<uint8_t> hsym(total_sym);
         for (int k = 0; k < n_strings; k++)
             if (sym_off[k + 1] > sym_off[k]) memcpy(hsym.data() + sym_off[k], symbols[k], sym_off[k + 1] - sym_off[k]);
         if (t->d_jobs.upload(jobs.data(), n_pairs, s) || t->d_slot_base.upload(slot_base.data(), n_pairs, s) ||
-            t->d_submat.upload(mat, 24 * 24, s) || t->d_sym.upload(hsym.data(), total_sym, s) || t->d_cnt.alloc(total_sym) ||
+            t->d_submat.upload(hsp_matrix(params, match_type), 24 * 24, s) || t->d_sym.upload(hsym.data(), total_sym, s) || t->d_cnt.alloc(total_sym) ||
             t->d_first.alloc(total_sym) || t->d_blocksum.alloc(blk_off[n_strings]) || t->d_total.upload(totals.data(), (size_t)n_strings, s)) return -1;
-        // 1. count: per string, as c4gpu_seed_scan
-        for (int k = 0; k < n_strings; k++) {
-            const int n = (int)(sym_off[k + 1] - sym_off[k]), n_blocks = (int)(blk_off[k + 1] - blk_off[k]);
-            if (!n) continue;
-            hipLaunchKernelGGL(seed_count_kernel, dim3(n_blocks), dim3(256), 0, s, t->d_sym.p + sym_off[k], n, t->width, t->wordlen,
-                               t->slots.p, t->mask, t->d_cnt.p + sym_off[k], t->d_first.p + sym_off[k], t->d_blocksum.p + blk_off[k]);
-            hipLaunchKernelGGL(seed_blockscan_kernel, dim3(1), dim3(1024), 0, s, t->d_blocksum.p + blk_off[k], n_blocks, t->d_total.p + k);
-        }
+        // 1. count, per string
+        for (int k = 0; k < n_strings; k++)
+            if (sym_off[k + 1] > sym_off[k]) seed_count_launch(t, s, sym_off[k], (int)(sym_off[k + 1] - sym_off[k]), blk_off[k], k);
         HIP_OK(hipGetLastError());
         if (t->d_total.download(totals.data(), (size_t)n_strings, s)) return -1;     // 8 bytes per string: they size the buffers
         HIP_OK(c4_stream_sync(s));
@@ -545,9 +526,9 @@ extern "C" int c4gpu_seed_extend(c4gpu_ctx *ctx, c4gpu_wordtab *t, const c4gpu_p
         }
         // 4. chains, 5. compaction
         const int chain_grid = (int)std::min<long long>((N + 63) / 64, 1 << 20);
-        hipLaunchKernelGGL(seed_chain_kernel, dim3(chain_grid), dim3(64), 0, s, seqs.qcode.p, seqs.tcode.p, t->d_jobs.p, t->d_seeds.p,
-                           t->d_keys[cur].p, t->d_vals[cur].p, N, (unsigned)n_slots, t->d_submat.p, aq, at, seedlen, dropoff, threshold,
-                           t->d_verdict.p, t->d_hsps.p);
+        const HspArgs a{seqs.qcode.p, seqs.tcode.p, nullptr, nullptr, t->d_jobs.p, aq, at, seedlen, dropoff, threshold};
+        hipLaunchKernelGGL(seed_chain_kernel, dim3(chain_grid), dim3(64), 0, s, a, t->d_seeds.p, t->d_keys[cur].p, t->d_vals[cur].p, N,
+                           (unsigned)n_slots, t->d_submat.p, t->d_verdict.p, t->d_hsps.p);
         hipLaunchKernelGGL(seed_verdict_count_kernel, dim3(n_tiles), dim3(256), 0, s, t->d_verdict.p, N, t->d_hist.p, t->d_report.p + 1);
         hipLaunchKernelGGL(seed_blockscan_kernel, dim3(1), dim3(1024), 0, s, t->d_hist.p, n_tiles, t->d_report.p + 2);
         hipLaunchKernelGGL(seed_compact_kernel, dim3(n_tiles), dim3(256), 0, s, t->d_verdict.p, N, t->d_hist.p, t->d_seeds.p, t->d_hsps.p,
