@@ -12,7 +12,7 @@ SO = os.path.join(ROOT, "build", "libc4kchoice.so")
 CSRC = os.path.join(ROOT, "exonerate_amd", "csrc")
 SRC = [os.path.join(ROOT, "tests", "kernel_choice_sim.hip")] + [os.path.join(CSRC, f)
                                                                  for f in ("c4_kernel_choice.h", "c4_launch.h", "c4_config.h")]
-FAMILY = {"affine": 1, "est2genome": 2, "protein2dna": 4, "protein2genome": 5}      # c4k::Family
+FAMILY = {"affine": 1, "est2genome": 2, "protein2dna": 4, "protein2genome": 5, "ner": 31}      # c4k::Family
 SCORE, PATH, REGION, CKPT = 0, 1, 2, 3                                               # c4k's MODE_*
 FACTS = ("family", "mode", "cont", "n", "blocked", "span", "local", "local_exact", "starts_pack", "cont_free", "seed_mode",
          "kshift", "fmt16", "pk16_params_ok", "pk16_all_fit", "tdense_n", "ss16_built", "cu_count")
@@ -40,6 +40,9 @@ def load():
         lib.kcsim_ck16_rooted.argtypes = [C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_char_p, C.c_int]
         lib.kcsim_pk16_enabled.restype = C.c_int
         lib.kcsim_pk16_enabled.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+        lib.kcsim_geometry.restype = C.c_int
+        lib.kcsim_geometry.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
+                                       C.c_char_p, C.c_int, C.POINTER(C.c_int)]
         _lib = lib
     return _lib
 
@@ -67,6 +70,41 @@ def choose(query_lengths, switches=None, **facts):
     if err:
         return "error", name.value.decode()
     return name.value.decode(), {k for b, k in enumerate(("fmt16", "needs_ss16", "staged_codes")) if flags.value >> b & 1}
+
+
+GEOMETRY = ("R", "waves", "hbm_carry", "staged_rows", "staged_rows6")
+PK16, WIN16, CK16, CK16_ROOTED = 1, 2, 3, 4               # kcsim_geometry's `which` for a kernel named by its form
+
+
+def _geometry(which, family, index, query_lengths, switches, facts):
+    facts.setdefault("n", len(query_lengths))
+    f = (C.c_int * len(FACTS))(*[int(facts.get(k, 0)) for k in FACTS])
+    send = [] if facts.get("cont") else query_lengths
+    q = (C.c_int * max(1, len(send)))(*send)
+    name = C.create_string_buffer(128)
+    geo = (C.c_int * len(GEOMETRY))()
+    err = load().kcsim_geometry(which, family, index, f, _switches(switches or {}), q, len(send), name, len(name), geo)
+    out = dict(zip(GEOMETRY, geo))
+    out["name"] = None if err else name.value.decode()
+    out["error"] = name.value.decode() if err else None
+    return out
+
+
+def geometry(query_lengths, switches=None, **facts):
+    """The kernel choose() names for the same arguments, with its geometry from the kernel table: {"name", "R" (query rows per
+    lane), "waves" (per job), "hbm_carry", "staged_rows", "staged_rows6" (pk16_staged_rows / _rows6), "error"}; name is None
+    and error the text where the launch cannot be served."""
+    if isinstance(query_lengths, tuple):
+        query_lengths = [query_lengths[0]] * query_lengths[1]
+    unknown = set(facts) - set(FACTS)
+    assert not unknown, unknown
+    return _geometry(0, 0, 0, query_lengths, switches, dict(facts))
+
+
+def form_geometry(which, family, index):
+    """The same for a kernel of the packed passes named by its form: which = PK16 (index: c4k::Pk16Form), WIN16 (Win16Shape), CK16
+    (Ck16Shape) or CK16_ROOTED (Ck16RootedShape); name None where the family has no such kernel."""
+    return _geometry(which, FAMILY[family], index, [], None, {})
 
 
 def ck16_rooted(strips, n_rooted, rows_max, switches=None):
