@@ -250,7 +250,7 @@ def _pairs(pairs):
 
 def _match_kind(match):
     return {"dna2dna": _abi.MATCH_DNA2DNA, "protein2protein": _abi.MATCH_PROTEIN2PROTEIN,
-            "protein2dna": _abi.MATCH_PROTEIN2DNA}[match]
+            "protein2dna": _abi.MATCH_PROTEIN2DNA, "codon2codon": _abi.MATCH_CODON2CODON}[match]
 
 
 def _hsp_seeds(seeds, chain=None, horizon0=None):
@@ -420,7 +420,7 @@ class Engine:
     def hsp_extend(self, params, match, pairs, seedlen, dropoff, seeds):
         """HSPset_seed_hsp's ungapped X-drop extension (hspset.c:933) of every seed (pair index, query_start,
         target_start) in one launch: [query_start, target_start, length, score, cobs] per seed.  `match`:
-        "dna2dna" | "protein2protein" | "protein2dna"."""
+        "dna2dna" | "protein2protein" | "protein2dna" | "codon2codon" (both advances 3, nucleotide positions)."""
         arr, keep = _pairs(pairs)
         cs, n = _hsp_seeds(seeds)
         out = (_abi.Hsp * max(1, n))()

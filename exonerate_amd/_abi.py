@@ -137,7 +137,7 @@ class SeedExtendStats(C.Structure):
     _fields_ = [("n_hits", C.c_int64), ("n_extended", C.c_int64), ("n_below", C.c_int64), ("n_kept", C.c_int64)]
 
 
-MATCH_DNA2DNA, MATCH_PROTEIN2PROTEIN, MATCH_PROTEIN2DNA = 0, 1, 2
+MATCH_DNA2DNA, MATCH_PROTEIN2PROTEIN, MATCH_PROTEIN2DNA, MATCH_CODON2CODON = 0, 1, 2, 3
 
 
 class Continuation(C.Structure):

@@ -45,7 +45,8 @@ __global__ void hsp_chain_kernel(const HspArgs a, const c4gpu_hsp_seed *__restri
 // Per position of the raw residues, is the strand position starting there masked (match.c:156-158,178-182,212-220)?  A
 // symbol is masked when the alphabet's SOFTMASK filter maps it elsewhere than TO_UPPER does (alphabet.h:87,
 // alphabet.c:124-129): every lower-case letter but the wildcard itself (`wild`: 'n' for DNA, 'x' for protein).  A strand of
-// advance 3 ORs its three bases; the last two positions of a sequence start no codon and are never read.  The coded arrays
+// advance 3 ORs its three bases (Match_3_mask_func: the target of PROTEIN2DNA, both sides of CODON2CODON); the last two
+// positions of a sequence start no codon and are never read.  The coded arrays
 // fold case away (Submat index), so this reads the raw bytes; built only for a side whose alphabet is soft-masked.
 __global__ void softmask_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, long long n, int advance, int wild) {
     for (long long x = blockIdx.x * (long long)blockDim.x + threadIdx.x; x < n; x += (long long)gridDim.x * blockDim.x) {
@@ -57,9 +58,14 @@ __global__ void softmask_kernel(const uint8_t *__restrict__ in, uint8_t *__restr
 }
 
 // what an HSPset of `match_type` reads: the coded arrays of a protein2dna batch are exactly what PROTEIN2DNA scoring reads
-// (row of the codon at each target position), the 1:1 matches use the plain residue rows
-int hsp_family(int match_type) { return match_type == C4GPU_MATCH_PROTEIN2DNA ? FAM_UNGAPPED_P2D : FAM_UNGAPPED; }
-int hsp_target_advance(int match_type) { return match_type == C4GPU_MATCH_PROTEIN2DNA ? 3 : 1; }
+// (row of the codon at each target position), those of an ungapped:trans batch hold such rows on both sides (CODON2CODON),
+// the 1:1 matches use the plain residue rows
+bool hsp_match_known(int match_type) { return match_type >= C4GPU_MATCH_DNA2DNA && match_type <= C4GPU_MATCH_CODON2CODON; }
+int hsp_family(int match_type) {
+    return match_type == C4GPU_MATCH_CODON2CODON ? FAM_UNGAPPED_CODON : match_type == C4GPU_MATCH_PROTEIN2DNA ? FAM_UNGAPPED_P2D : FAM_UNGAPPED;
+}
+int hsp_query_advance(int match_type) { return match_type == C4GPU_MATCH_CODON2CODON ? 3 : 1; }
+int hsp_target_advance(int match_type) { return match_type == C4GPU_MATCH_PROTEIN2DNA || match_type == C4GPU_MATCH_CODON2CODON ? 3 : 1; }
 const int32_t *hsp_matrix(const c4gpu_params *params, int match_type) {
     return match_type == C4GPU_MATCH_DNA2DNA ? &params->dna_submat[0][0] : &params->protein_submat[0][0];
 }
@@ -77,10 +83,10 @@ int hsp_extend_host(const char *who, c4gpu_ctx *ctx, const c4gpu_params *params,
                     c4gpu_hsp *out, int32_t *dropped) {
     try {
         if (hipSetDevice(ctx->device) != hipSuccess) return -1;
-        if (match_type < C4GPU_MATCH_DNA2DNA || match_type > C4GPU_MATCH_PROTEIN2DNA) { c4h::set_error("unknown match type"); return -1; }
+        if (!hsp_match_known(match_type)) { c4h::set_error("unknown match type"); return -1; }
         if (!n_seeds) return 0;
         const bool masked = dropped != nullptr;
-        const int aq = 1, at = hsp_target_advance(match_type);
+        const int aq = hsp_query_advance(match_type), at = hsp_target_advance(match_type);
         std::vector<int> first, order;
         if (chain) { first.assign((size_t)n_chains + 1, 0); order.resize((size_t)n_seeds); }
         for (int k = 0; k < n_seeds; k++) {
@@ -107,7 +113,7 @@ int hsp_extend_host(const char *who, c4gpu_ctx *ctx, const c4gpu_params *params,
         if (masked && mask_query) {
             if (qmask.alloc((size_t)hq_n)) return -1;
             hipLaunchKernelGGL(softmask_kernel, dim3(1024), dim3(256), 0, s, seqs.qraw.p, qmask.p, hq_n, aq,
-                               match_type == C4GPU_MATCH_DNA2DNA ? 'n' : 'x');
+                               match_type == C4GPU_MATCH_DNA2DNA || match_type == C4GPU_MATCH_CODON2CODON ? 'n' : 'x');
         }
         if (masked && mask_target) {
             if (tmask.alloc((size_t)ht_n)) return -1;

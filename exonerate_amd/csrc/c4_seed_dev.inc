@@ -140,8 +140,8 @@ __global__ __launch_bounds__(256) void seed_fill_kernel(int n, const int *__rest
 // ---- c4gpu_seed_extend: the hits stay here and become the HSPs a fresh HSPset per pair would store ---------------------
 // The scan above gives every hit its walk index; what HSPset_seed_hsp (hspset.c:933-997) then does hit by hit depends on the
 // order only through the horizon entry the seed is tested against (:939-958) and moves (:990).  So: every hit becomes a seed
-// with the number of its entry (its slot: all entries of all pairs numbered through, slot_base[pair] + section * at + tf, or
-// n_slots for a seed without one); a stable radix sort groups the walk indices by slot, walk order kept inside a slot; one
+// with the number of its entry (its slot: all entries of all pairs numbered through, slot_base[pair] + (section * aq + qf) * at
+// + tf, or n_slots for a seed without one); a stable radix sort groups the walk indices by slot, walk order kept inside a slot; one
 // lane per run of equal slots replays that entry alone (hsp_horizon_step, c4_hsp_extend.h); a prefix sum over the kept
 // verdicts in walk-index order lays the kept HSPs out as HSP_store met them.
 
@@ -150,7 +150,8 @@ __global__ __launch_bounds__(256) void seed_expand_kernel(int n, const int *__re
                                                           const unsigned long long *__restrict__ blockoff, unsigned long long hit_base,
                                                           unsigned long long n_hits, const c4gpu_seed_emit *__restrict__ emits,
                                                           const HspJob *__restrict__ jobs, const unsigned *__restrict__ slot_base,
-                                                          int scale, int offset, int modifier, int at, int seedlen, unsigned n_slots,
+                                                          int scale, int offset, int modifier, int aq, int at, int seedlen,
+                                                          unsigned n_slots,
                                                           c4gpu_hsp_seed *__restrict__ seeds, unsigned *__restrict__ keys,
                                                           int *__restrict__ vals, unsigned long long *__restrict__ outside,
                                                           unsigned long long *__restrict__ first_hit) {
@@ -162,13 +163,20 @@ __global__ __launch_bounds__(256) void seed_expand_kernel(int n, const int *__re
         if (pos < first_hit[em.pair]) atomicMin(&first_hit[em.pair], pos);      // (it only ever falls: a stale read is too large)
         unsigned key = n_slots;
         int pair = em.pair;
-        if (ts < 0 || jb.qlen <= 0 || em.query_pos + seedlen > jb.qlen || (long long)ts + (long long)seedlen * at > jb.tlen) {
+        if (ts < 0 || jb.qlen <= 0 || (long long)em.query_pos + (long long)seedlen * aq > jb.qlen ||
+            (long long)ts + (long long)seedlen * at > jb.tlen) {
             *outside = 1;                                            // the call fails; the seed is never read through
             pair = -1;
-        } else {
+        } else if (aq == 1) {
             const int diag = ts - em.query_pos * at;                 // hspset.c:941-944 (query advance 1)
             const int section = (diag + jb.qlen) % jb.qlen;          // C's remainder: negative above the main diagonal's reach
             if (section >= 0) key = slot_base[em.pair] + (unsigned)section * (unsigned)at + (unsigned)(ts % at);
+        } else {
+            // both advances 3 (CODON2CODON).  Sequence.len is unsigned, so the reference's sum and remainder are (hspset.c:935-943):
+            // a seed more than qlen under the main diagonal wraps to an entry another diagonal owns, and has one like any other
+            const unsigned sum = (unsigned)ts * (unsigned)aq - (unsigned)em.query_pos * (unsigned)at + (unsigned)jb.qlen;
+            const unsigned section = sum % (unsigned)jb.qlen;
+            key = slot_base[em.pair] + (section * (unsigned)aq + (unsigned)(em.query_pos % aq)) * (unsigned)at + (unsigned)(ts % at);
         }
         seeds[pos] = c4gpu_hsp_seed{pair, em.query_pos, ts};
         keys[pos] = key;
@@ -444,7 +452,7 @@ extern "C" int c4gpu_seed_extend(c4gpu_ctx *ctx, c4gpu_wordtab *t, const c4gpu_p
     try {
         *stats = c4gpu_seed_extend_stats{0, 0, 0, 0};
         if (hipSetDevice(ctx->device) != hipSuccess) { c4h::set_error("hipSetDevice failed"); return -1; }
-        if (match_type < C4GPU_MATCH_DNA2DNA || match_type > C4GPU_MATCH_PROTEIN2DNA) { c4h::set_error("unknown match type"); return -1; }
+        if (!hsp_match_known(match_type)) { c4h::set_error("unknown match type"); return -1; }
         if (!t->emits_set) { c4h::set_error("c4gpu_seed_extend: no emissions set (c4gpu_wordtab_set_emissions)"); return -1; }
         if (t->emit_max_pair >= n_pairs) { c4h::set_error("c4gpu_seed_extend: an emission names a pair outside `pairs`"); return -1; }
         if (n_pairs < 0 || n_strings < 0 || tpos_scale < 1 || seedlen < 1) { c4h::set_error("c4gpu_seed_extend: bad shape"); return -1; }
@@ -453,12 +461,12 @@ extern "C" int c4gpu_seed_extend(c4gpu_ctx *ctx, c4gpu_wordtab *t, const c4gpu_p
                 c4h::set_error("c4gpu_seed_extend: the pairs do not all name one target buffer and length");
                 return -1;
             }
-        const int aq = 1, at = hsp_target_advance(match_type);
+        const int aq = hsp_query_advance(match_type), at = hsp_target_advance(match_type);
         long long n_slots = 0;
         std::vector<unsigned> slot_base((size_t)std::max(1, n_pairs));
         for (int i = 0; i < n_pairs; i++) {
             slot_base[i] = (unsigned)n_slots;
-            n_slots += (long long)std::max(0, pairs[i].query_len) * at;
+            n_slots += (long long)std::max(0, pairs[i].query_len) * aq * at;
             if (n_slots > 0x7fffffffLL) { c4h::set_error("c4gpu_seed_extend: more than 2^31 - 1 horizon entries"); return -1; }
         }
         // the strings behind each other in one buffer, each with whole count blocks of its own
@@ -512,7 +520,7 @@ extern "C" int c4gpu_seed_extend(c4gpu_ctx *ctx, c4gpu_wordtab *t, const c4gpu_p
             if (!n || !totals[k]) continue;
             hipLaunchKernelGGL(seed_expand_kernel, dim3(n_blocks), dim3(256), 0, s, n, t->d_cnt.p + sym_off[k], t->d_first.p + sym_off[k],
                                t->d_blocksum.p + blk_off[k], hit_base[k], n_hits, t->d_emits.p, t->d_jobs.p, t->d_slot_base.p, tpos_scale,
-                               tpos_offset ? tpos_offset[k] : 0, tpos_modifier, at, seedlen, (unsigned)n_slots, t->d_seeds.p,
+                               tpos_offset ? tpos_offset[k] : 0, tpos_modifier, aq, at, seedlen, (unsigned)n_slots, t->d_seeds.p,
                                t->d_keys[0].p, t->d_vals[0].p, t->d_report.p, t->d_first_hit.p);
         }
         // 3. group by slot: keys run to n_slots (the seeds without an entry)

@@ -448,8 +448,10 @@ void         c4gpu_stage_destroy(c4gpu_stage *st);
 /* ---- HSP seeding (src/comparison/hspset.c) ------------------------------------------------------------------------ */
 
 /* Match_Type of an HSPset (src/comparison/match.h:45-51): what one HSP position scores.  DNA2DNA: dna submat[q][t];
- * PROTEIN2PROTEIN: protein submat[q][t]; PROTEIN2DNA: protein submat[q][aa(t, t+1, t+2)], target advance 3. */
-enum { C4GPU_MATCH_DNA2DNA = 0, C4GPU_MATCH_PROTEIN2PROTEIN = 1, C4GPU_MATCH_PROTEIN2DNA = 2 };
+ * PROTEIN2PROTEIN: protein submat[q][t]; PROTEIN2DNA: protein submat[q][aa(t, t+1, t+2)], target advance 3;
+ * CODON2CODON (match.c:508-539, the seeds of ungapped:trans and coding2coding): protein submat[aa(q, q+1, q+2)][aa(t, t+1, t+2)],
+ * both advances 3 -- positions are nucleotide positions, a seed of seedlen codons covers 3 * seedlen of them on either side. */
+enum { C4GPU_MATCH_DNA2DNA = 0, C4GPU_MATCH_PROTEIN2PROTEIN = 1, C4GPU_MATCH_PROTEIN2DNA = 2, C4GPU_MATCH_CODON2CODON = 3 };
 
 /* one word hit handed to HSPset_seed_hsp (hspset.c:933): positions in pair `pair` */
 typedef struct { int32_t pair, query_start, target_start; } c4gpu_hsp_seed;
@@ -459,7 +461,9 @@ typedef struct { int32_t query_start, target_start, length, score, cobs; } c4gpu
 
 /* The ungapped X-drop extension of every seed, on the device: what HSPset_seed_hsp computes for a seed its horizon lets
  * through (the horizon, the threshold and the store order stay with the caller: they need the HSPs in seed order).
- * seedlen / dropoff: HSP_Param.seedlen / .dropoff.  Fails (-1) on residues outside the submat alphabet. */
+ * seedlen / dropoff: HSP_Param.seedlen / .dropoff.  A seed must lie inside its pair: query_start + seedlen * query advance
+ * <= query_len, and the same on the target (the advances of `match_type`, above).  Fails (-1) on residues outside the submat
+ * alphabet and on a match type that is none of the four. */
 int         c4gpu_hsp_extend_batch(c4gpu_ctx *ctx, const c4gpu_params *params, int match_type,
                                    const c4gpu_pair *pairs, int32_t n_pairs, int32_t seedlen, int32_t dropoff,
                                    const c4gpu_hsp_seed *seeds, int32_t n_seeds, c4gpu_hsp *out);
@@ -478,7 +482,8 @@ int         c4gpu_hsp_extend_chains(c4gpu_ctx *ctx, const c4gpu_params *params, 
  * mask_query / mask_target: is that side's alphabet soft-masked (Alphabet.is_soft_masked); a lower-case residue on a side
  * whose flag is 0 is NOT masked (Alphabet_is_masked, alphabet.h:87).  On a flagged side a position is masked when its symbol
  * is lower case and not the wildcard itself ('n' for DNA, 'x' for protein: alphabet.c:124-129 maps those where TO_UPPER does);
- * a PROTEIN2DNA target position when any of its three bases is (match.c:212-220).  threshold: HSP_Param.threshold.
+ * a PROTEIN2DNA target position, and a CODON2CODON position on either side (wildcard 'n'), when any of its three bases is
+ * (Match_3_mask_func, match.c:212-220).  threshold: HSP_Param.threshold.
  *   stage 1  HSP_extend(forbid_masked = TRUE) (hspset.c:762-765,794-797): each direction stops in front of the first masked
  *            position.  If the score is then below `threshold` the seed is DROPPED: dropped[k] = 1 and out[k] holds the
  *            masked-extended HSP (query_start, target_start, length, score; cobs = 0).  Nothing is stored for it, and the
@@ -534,7 +539,14 @@ void        c4gpu_wordtab_stats(const c4gpu_wordtab *t, double *scan_ms, int64_t
  * nothing.  Every other seed is skipped when target_start lies below entry (pair, section, tf) -- keyed by SECTION as in the
  * reference, so protein-vs-DNA diagonals qlen bases apart share one -- and otherwise extended; the entry becomes
  * hsp.target_start + hsp.length * at whether or not the HSP reaches `threshold`.  Kept = extended with score >= threshold
- * (HSP_store).  out: the kept HSPs in walk order, `seed` = index of the word hit in walk order over all strings; when
+ * (HSP_store).
+ * CODON2CODON (aq = at = 3; the word table's query positions are nucleotide positions, seeder.c:540-545): diag = target_start * aq
+ * - query_start * at; qlen * aq * at entries per pair, entry (section * aq + query_start % aq) * at + tf; a seed lies inside its pair
+ * when query_pos + seedlen * aq <= qlen.  Its section follows the reference's arithmetic to the letter: Sequence.len is unsigned
+ * (sequence.h:83), so (diag + qlen) % qlen is taken in 32-bit UNSIGNED arithmetic (hspset.c:942-943) and a seed with a negative
+ * sum -- any hit with 3 * (query_start - target_start) > qlen, the lower-left third of the rectangle -- is not left without an entry but lands on entry
+ * (uint32)(diag + qlen) % qlen, which it shares with another diagonal.  The 1/1 and 1/3 forms above keep "no entry" there.
+ * out: the kept HSPs in walk order, `seed` = index of the word hit in walk order over all strings; when
  * stats->n_kept exceeds cap nothing is written and the call returns 0 (come back with more room, as for c4gpu_seed_scan).
  * Fails (-1): unknown match type; no emissions set or their number is not the table's; an emission naming no pair or a
  * negative query position; pairs of different targets; a seed outside its pair; more than 2^31 - 1 hits or horizon entries;

@@ -13,8 +13,11 @@
  * Soft-masked sets (--softmaskquery / --softmasktarget) take the two-stage rule of hspset.c:981-995 on the device
  * (c4gpu_hsp_extend_batch_masked / _chains_masked): a seed whose masked extension stays below the threshold is DROPPED, the
  * replay stores nothing for it and moves the horizon to its masked end.
- * Not taken: --seedrepeat > 1, HSPsets without a horizon, match types other than DNA / protein / protein-vs-DNA: those
- * sets keep the reference's own function.
+ * C4GPU_CODON_SEED=1 (opt-in): the codon sets of ungapped:trans and coding2coding are taken too (C4GPU_MATCH_CODON2CODON, both
+ * advances 3, soft-masked ones included) -- but not a set whose query carries an annotation.
+ * Not taken: --seedrepeat > 1, HSPsets without a horizon, match types other than DNA / protein / protein-vs-DNA (and, with the
+ * switch, codon-vs-codon): those sets keep the reference's own function.
+ * C4GPU_HSP_DUMP=FILE: every flushed set as one JSON line (hsp_dump_set).
  * C4GPU_HSP_HOST=1 (CPU test of the seam): the extensions come from the reference's own HSPset_seed_hsp on scratch sets.
  * C4GPU_HSP_CHECK=1: after the device call every extended seed is compared with that function's result (kept or dropped,
  * ends, score, masked end); the run aborts at the first difference. */
@@ -37,13 +40,41 @@ static GHashTable *hsp_pending = NULL;          /* HSPset* -> ShimSeedSet* */
 static GPtrArray *hsp_order = NULL;             /* ShimSeedSet*, in order of first seed */
 static struct { long sets, seeds, stored, dropped, checked, flushes; double device_ms; } hst;
 
+/* C4GPU_CODON_SEED=1 (opt-in): the seeds of the translated models (ungapped:trans, coding2coding) are taken too */
+gboolean shim_codon_seed(void){
+    static gint on = -1;
+    if(on < 0)
+        on = (shim_env("C4GPU_CODON_SEED") && atoi(shim_env("C4GPU_CODON_SEED"))) ? 1 : 0;
+    return on;
+    }
+
 static gint hsp_match_kind(HSPset *hsp_set){
     switch(hsp_set->param->match->type){
         case Match_Type_DNA2DNA: return C4GPU_MATCH_DNA2DNA;
         case Match_Type_PROTEIN2PROTEIN: return C4GPU_MATCH_PROTEIN2PROTEIN;
         case Match_Type_PROTEIN2DNA: return C4GPU_MATCH_PROTEIN2DNA;
+        /* behind the switch; a query with an annotation keeps the reference's function, which vetoes codons outside the CDS
+         * frame inside the score (Match_3_3_split_score_func, match.c:513-519) */
+        case Match_Type_CODON2CODON: return (shim_codon_seed() && !hsp_set->query->annotation) ? C4GPU_MATCH_CODON2CODON : -1;
         default: return -1;
         }
+    }
+
+static const gchar *hsp_match_name(HSPset *hsp_set){
+    switch(hsp_set->param->match->type){
+        case Match_Type_DNA2DNA: return "dna2dna";
+        case Match_Type_PROTEIN2PROTEIN: return "protein2protein";
+        case Match_Type_PROTEIN2DNA: return "protein2dna";
+        case Match_Type_CODON2CODON: return "codon2codon";
+        default: return "other";
+        }
+    }
+
+/* hspset.c:935-943 as the reference computes it: Sequence.len is a guint, so the sum and the remainder are unsigned */
+static gint hsp_section(HSPset *hsp_set, guint query_start, guint target_start){
+    register gint diag_pos = (target_start * hsp_set->param->match->query->advance)
+                           - (query_start * hsp_set->param->match->target->advance);
+    return (diag_pos + hsp_set->query->len) % hsp_set->query->len;
     }
 
 static gboolean hsp_eligible(HSPset *hsp_set){
@@ -194,6 +225,57 @@ static void hsp_replay(ShimSeedSet *ss, const c4gpu_hsp *hsp, const gint32 *drop
     return;
     }
 
+/* C4GPU_HSP_DUMP=FILE: one JSON line per set and flush -- what the set was given, what the reference's own function makes of
+ * every seed by itself (hsp_host_one: [query_start, target_start, length, score, cobs, dropped]; a dropped seed carries its
+ * masked end as target_start and length 0), and the HSPs the set holds after the replay (before it is finalised: with
+ * --hspfilter they wait in the filter queues and are not listed).  tools/make_codon_hsp_golden.py turns it into fixtures. */
+static void hsp_dump_str(FILE *fp, const gchar *s){
+    fputc('"', fp);
+    for(; *s; s++)
+        if((*s != '"') && (*s != '\\') && ((guchar)*s >= 0x20))
+            fputc(*s, fp);
+    fputc('"', fp);
+    return;
+    }
+
+static void hsp_dump_set(ShimSeedSet *ss, const gchar *qstr, const gchar *tstr){
+    static FILE *fp = NULL;
+    register HSPset *set = ss->set;
+    register guint k;
+    if(!fp && !(fp = fopen(shim_env("C4GPU_HSP_DUMP"), "a")))
+        g_error("C4GPU_HSP_DUMP: cannot open [%s]", shim_env("C4GPU_HSP_DUMP"));
+    fprintf(fp, "{\"query_id\":");
+    hsp_dump_str(fp, set->query->id);
+    fprintf(fp, ",\"target_id\":");
+    hsp_dump_str(fp, set->target->id);
+    fprintf(fp, ",\"match\":\"%s\",\"seedlen\":%d,\"dropoff\":%d,\"threshold\":%d,\"query_advance\":%d,\"target_advance\":%d,"
+                "\"seed_repeat\":%d,\"mask_query\":%s,\"mask_target\":%s,\"query\":", hsp_match_name(set), (gint)set->param->seedlen,
+            (gint)set->param->dropoff, (gint)set->param->threshold, (gint)set->param->match->query->advance,
+            (gint)set->param->match->target->advance, (gint)set->param->seed_repeat,
+            set->query->alphabet->is_soft_masked ? "true" : "false", set->target->alphabet->is_soft_masked ? "true" : "false");
+    hsp_dump_str(fp, qstr);
+    fprintf(fp, ",\"target\":");
+    hsp_dump_str(fp, tstr);
+    fprintf(fp, ",\"seeds\":[");
+    for(k = 0; k < ss->seeds->len; k++)
+        fprintf(fp, "%s[%u,%u]", k ? "," : "", g_array_index(ss->seeds, guint, 2 * k), g_array_index(ss->seeds, guint, 2 * k + 1));
+    fprintf(fp, "],\"single\":[");
+    for(k = 0; k < ss->seeds->len; k++){
+        c4gpu_hsp h;
+        gint32 d;
+        hsp_host_one(set, g_array_index(ss->seeds, guint, 2 * k), g_array_index(ss->seeds, guint, 2 * k + 1), &h, &d);
+        fprintf(fp, "%s[%d,%d,%d,%d,%d,%d]", k ? "," : "", h.query_start, h.target_start, h.length, h.score, h.cobs, d);
+        }
+    fprintf(fp, "],\"set\":[");
+    for(k = 0; k < set->hsp_list->len; k++){
+        register HSP *h = set->hsp_list->pdata[k];
+        fprintf(fp, "%s[%u,%u,%u,%d,%u]", k ? "," : "", h->query_start, h->target_start, h->length, (gint)h->score, h->cobs);
+        }
+    fprintf(fp, "]}\n");
+    fflush(fp);
+    return;
+    }
+
 static void hsp_flush(void){
     register guint i, k, n_sets = hsp_order ? hsp_order->len : 0, total = 0;
     register GHashTable *seq_index;
@@ -261,7 +343,8 @@ static void hsp_flush(void){
                 register guint *seed = &g_array_index(ss->seeds, guint, 2 * k);
                 register gint diag_pos = (seed[1] * aq) - (seed[0] * at);
                 register gint qf = seed[0] % aq, tf = seed[1] % at;
-                register gint section_pos = (diag_pos + qlen) % qlen;
+                /* (a codon set's wrapped seeds -- the common case there -- are on the entry the replay will find them on) */
+                register gint section_pos = (aq > 1) ? hsp_section(set, seed[0], seed[1]) : (diag_pos + qlen) % qlen;
                 gint32 h;
                 if(section_pos < 0){                          /* no horizon entry (see hsp_replay): never skipped */
                     h = G_MININT32;
@@ -365,6 +448,8 @@ static void hsp_flush(void){
             for(k = 0; k < ss->seeds->len; k++)
                 HSPset_seed_hsp_cpu(ss->set, g_array_index(ss->seeds, guint, 2 * k), g_array_index(ss->seeds, guint, 2 * k + 1));
             }
+        if(shim_env("C4GPU_HSP_DUMP"))
+            hsp_dump_set(ss, g_hash_table_lookup(seq_index, ss->set->query), g_hash_table_lookup(seq_index, ss->set->target));
         hst.sets++; hst.seeds += ss->seeds->len;
         g_array_free(ss->seeds, TRUE);
         g_free(ss);

@@ -16,9 +16,12 @@
  *   3. the report loop of Seeder_add_target (seeder.c:899-913) follows unchanged.
  * Building the automaton (Seeder_add_query, word neighbourhoods) stays the reference's.  Not taken (the reference's own
  * function runs): --saturatethreshold (a per-word running count in walk order), --wordambiguity > 1, seeders with both
- * a DNA and a codon loader, a seeder whose automaton was compiled before this front saw it.
+ * a DNA and a codon loader, a seeder whose automaton was compiled before this front saw it, and -- unless C4GPU_CODON_SEED=1
+ * (opt-in) -- a seeder with a translated query (ungapped:trans, coding2coding: the words of the query's three frames in one
+ * automaton, their seeds' query positions nucleotide positions already, seeder.c:540-545; the table reads them as they are).
  * C4GPU_SEED_FUSED=1 (opt-in): where every emission of the table belongs to one loader whose HSP_Param
- * the seeding seam would take (a horizon, seed_repeat 1, DNA / protein / protein-vs-DNA, no soft-masked alphabet) step 2 is ONE
+ * the seeding seam would take (a horizon, seed_repeat 1, DNA / protein / protein-vs-DNA -- with C4GPU_CODON_SEED=1 also
+ * codon-vs-codon without an annotated query --, no soft-masked alphabet) step 2 is ONE
  * c4gpu_seed_extend call per target -- scan, horizon test, extension and threshold on the device, the hits never leaving it --
  * and only the HSPs a fresh HSPset per query would store come back, in walk order; each goes to HSPset_add_known_hsp of its
  * query's set; the Comparisons are created in the order of the queries' first word hits (c4gpu_seed_extend_first_hits), which is
@@ -423,6 +426,7 @@ static gint seed_match_kind(HSP_Param *param){
         case Match_Type_DNA2DNA: return C4GPU_MATCH_DNA2DNA;
         case Match_Type_PROTEIN2PROTEIN: return C4GPU_MATCH_PROTEIN2PROTEIN;
         case Match_Type_PROTEIN2DNA: return C4GPU_MATCH_PROTEIN2DNA;
+        case Match_Type_CODON2CODON: return shim_codon_seed() ? C4GPU_MATCH_CODON2CODON : -1;
         default: return -1;
         }
     }
@@ -433,6 +437,7 @@ static void seed_fused_look(ShimSeedTab *st){
     register GHashTable *index;
     register Seeder_Loader *loader = NULL;
     register guint k;
+    register gboolean codon;
     st->fused_looked = TRUE;
     if(!st->emits->len)
         return;
@@ -444,13 +449,15 @@ static void seed_fused_look(ShimSeedTab *st){
         }
     if((!loader->hsp_param->use_horizon) || (loader->hsp_param->seed_repeat > 1) || (seed_match_kind(loader->hsp_param) < 0))
         return;
+    codon = (loader->hsp_param->match->type == Match_Type_CODON2CODON);
     index = g_hash_table_new(g_direct_hash, g_direct_equal);
     st->fused_query = g_new0(gchar*, seeder->query_info_list->len + 1);
     for(k = 0; k < seeder->query_info_list->len; k++){
         register Seeder_QueryInfo *query_info = seeder->query_info_list->pdata[k];
         g_hash_table_insert(index, query_info, GINT_TO_POINTER(k + 1));
         st->fused_query[k] = Sequence_get_str(query_info->query);
-        if(query_info->query->alphabet->is_soft_masked)
+        /* (an annotated query of a codon loader: its sets keep the reference's function, hsp_match_kind in c4gpu_hsp.c) */
+        if(query_info->query->alphabet->is_soft_masked || (codon && query_info->query->annotation))
             loader = NULL;
         }
     st->fused_emits = g_new(c4gpu_seed_emit, st->emits->len);
@@ -535,7 +542,7 @@ static gboolean seed_fused_host(ShimSeedTab *st, Sequence *target, gchar **strs,
                                 c4gpu_seed_hsp **kept, c4gpu_seed_extend_stats *stats, gint64 *first_hit){
     register Seeder *seeder = st->seeder;
     register HSP_Param *param = st->fused_loader->hsp_param;
-    register gint n_pairs = seeder->query_info_list->len, i, at = param->match->target->advance;
+    register gint n_pairs = seeder->query_info_list->len, i, aq = param->match->query->advance, at = param->match->target->advance;
     register HSPset **scratch = g_new0(HSPset*, n_pairs + 1);
     register GArray *out = g_array_new(FALSE, FALSE, sizeof(c4gpu_seed_hsp));
     register gint keep_filter = param->has->filter_threshold;
@@ -550,8 +557,9 @@ static gboolean seed_fused_host(ShimSeedTab *st, Sequence *target, gchar **strs,
             register c4gpu_seed_emit *e = &st->fused_emits[fh.hits[k].emit];
             register Seeder_QueryInfo *query_info = seeder->query_info_list->pdata[e->pair];
             register gint tpos = (fh.frame ? (fh.hits[k].pos * 3) + fh.frame - 1 : fh.hits[k].pos) - st->fused_loader->tpos_modifier;
-            register gint qlen = query_info->query->len, diag_pos = tpos - (e->query_pos * at);
-            register gint section_pos = (diag_pos + qlen) % qlen;
+            register gint qlen = query_info->query->len, diag_pos = (tpos * aq) - (e->query_pos * at);
+            /* a codon loader (aq 3): the reference's own unsigned sum and remainder (hspset.c:942-943), as c4gpu_seed_extend has it */
+            register gint section_pos = (aq > 1) ? (gint)(((guint)diag_pos + (guint)qlen) % (guint)qlen) : (diag_pos + qlen) % qlen;
             register HSPset *set;
             register guint before;
             if(first_hit[e->pair] < 0)
@@ -564,7 +572,7 @@ static gboolean seed_fused_host(ShimSeedTab *st, Sequence *target, gchar **strs,
                 set = scratch[e->pair];
                 }
             before = set->hsp_list->len;
-            if((section_pos < 0) || (tpos >= set->horizon[0][section_pos][0][tpos % at]))
+            if((section_pos < 0) || (tpos >= set->horizon[0][section_pos][e->query_pos % aq][tpos % at]))
                 stats->n_extended++;
             HSPset_seed_hsp_cpu(set, e->query_pos, tpos);
             if(set->hsp_list->len > before){
@@ -694,8 +702,9 @@ void Seeder_add_target(Seeder *seeder, Sequence *target){
     if(off < 0)
         off = (shim_env("C4GPU_SEED_OFF") || (shim_batch_size() <= 0)) ? 1 : 0;
     shim_mark("Seeder_add_target");
-    /* a translated query (codon2codon: match advance 3 on the query) has a word list per query frame: the reference's walk */
-    if((!off) && (match->query->advance == 1) && (shim_env("C4GPU_SEED_HOST") || shim_ctx_nowait())){
+    /* a translated query (codon2codon: match advance 3 on the query) has a word list per query frame, all in one automaton, its
+     * seeds' query positions already nucleotide positions (seeder.c:540-545): the reference's walk unless C4GPU_CODON_SEED=1 */
+    if((!off) && ((match->query->advance == 1) || shim_codon_seed()) && (shim_env("C4GPU_SEED_HOST") || shim_ctx_nowait())){
         st = seed_state(seeder);
         if(st->hopeless)
             st = NULL;

@@ -31,6 +31,7 @@ void shim_params(Ungapped_Data *ud, c4gpu_params *p);
 void shim_hsp_params(c4gpu_params *p);
 /* c4gpu_hsp.c */
 void shim_hsp_report(void);
+gboolean shim_codon_seed(void);        /* C4GPU_CODON_SEED=1: the HSP and word-scan seams take the translated models' seeds */
 /* c4gpu_bsdp.c */
 void shim_bsdp_flush(void);
 void shim_bsdp_report(void);
