@@ -469,8 +469,11 @@ class Engine:
     def sdp(self, model, pairs, hsps, query_advance=1, target_advance=1, dropoff=50, threshold=100, max_alignments=4):
         """The reference's default gapped-extension heuristic (SDP, GAM_Result_SDP_create gam.c:852) for a batch: per pair
         the list of alignments found from its HSPs ([query_start, target_start, length, score, cobs] each), both
-        Scheduler passes on the device (c4gpu_sdp_batch: one sparse wavefront per pair, both SDP flavours).  A pair the
-        device could not serve (its traceback did not fit the device's memory) yields None."""
+        Scheduler passes on the device (c4gpu_sdp_batch: one sparse wavefront per pair, both SDP flavours).  Served
+        models: affine, protein2dna, coding2coding (seeded flavour; coding2coding with query advances up to 3, HSPs of
+        either its DNA set, advances 1/1, or its codon set, 3/3), est2genome, protein2genome (boundary flavour); any
+        other raises C4GpuError.  A pair the device could not serve (its traceback did not fit the device's memory)
+        yields None."""
         arr, keep = _pairs(pairs)
         flat = [h for hs in hsps for h in hs]
         first = [0]

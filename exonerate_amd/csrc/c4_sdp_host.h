@@ -41,7 +41,8 @@ inline void make_kparams(const c4gpu_model *m, const c4gpu_params *params, KPara
     kp->start_scope = m->start_scope; kp->end_scope = m->end_scope;
     bool protein = false;
     for (int i = 0; i < m->n_calcs; i++)
-        if (m->calcs[i].kind == C4GPU_CALC_MATCH_PROTEIN || m->calcs[i].kind == C4GPU_CALC_MATCH_P2D) protein = true;
+        if (m->calcs[i].kind == C4GPU_CALC_MATCH_PROTEIN || m->calcs[i].kind == C4GPU_CALC_MATCH_P2D ||
+            m->calcs[i].kind == C4GPU_CALC_MATCH_CODON) protein = true;
     memcpy(kp->submat, protein ? &params->protein_submat[0][0] : &params->dna_submat[0][0], sizeof(int) * 24 * 24);
     for (int c = 0; c < 4096; c++) {
         const uint8_t row = params->submat_index[params->aa[params->trans[c]]];

@@ -16,6 +16,9 @@
 //     advance the query by 0 or 1: the (u, v - at) sources sit in the lane's own ring of earlier cells (VGPRs), the
 //     (u - 1, v - at) sources in the ring of the lane above, fetched once per step with DPP wave_shr:1.  Lane 0's upper
 //     neighbour is the bottom row of the strip before, which that strip left behind as a sparse list of live cells.
+//     A model whose transitions advance the query by up to 3 (coding2coding: seeded flavour only) keeps one such ring per
+//     advance ("hop"): hop a + 1 is the lane above's hop a of the step before, again one wave_shr:1, and holds (u - a - 1, v).
+//     The strip before then leaves its last MAXAQ rows behind, the cells of one column in one entry of the list.
 //   * A strip's sweep is event driven: it starts at the first step that holds a seed, a boundary cell or a live cell of
 //     the carried row, runs while anything in the rings is alive, and jumps to the next event when everything is dead.
 //     Steps in which no cell is alive leave nothing behind.  The work is the reference's own (cells inside the X-drop),
@@ -139,11 +142,16 @@ struct Plan {
     static_assert(adv_below_stat(), "advancing transitions must precede the static ones");
     static_assert(cb_is_static(), "the call-back state is entered by static transitions only");
     static_assert(STAT.n <= 16, "one bit per static transition in the cell's sweep record");
-    static_assert(M::MAXAQ == 1, "lanes exchange one query row per step");
+    static_assert(M::MAXAQ >= 1 && M::MAXAQ <= M::MAXAT + 1, "a strip's last MAXAQ rows are read back out of the lanes' own rings");
     // states whose value crosses to the lane below (sources of transitions that advance the query)
     static constexpr bool exported(int s) { for (int k = 0; k < NT; k++) if (is_adv(k) && M::tr[k].aq && src(k) == s) return true; return false; }
     static constexpr int n_exported() { int n = 0; for (int s = 0; s < NS; s++) n += exported(s); return n; }
     static constexpr int exported_index(int s) { int n = 0; for (int x = 0; x < s; x++) n += exported(x); return n; }
+    // ... and `a` lanes down (hop a): hop a + 1 is made of hop a, so a state travels as far as its widest transition reaches
+    static constexpr bool exported_hop(int s, int a) { for (int k = 0; k < NT; k++) if (is_adv(k) && M::tr[k].aq >= a && src(k) == s) return true; return false; }
+    static constexpr int n_exported_hop(int a) { int n = 0; for (int s = 0; s < NS; s++) n += exported_hop(s, a); return n; }
+    static constexpr int exported_hop_index(int s, int a) { int n = 0; for (int x = 0; x < s; x++) n += exported_hop(x, a); return n; }
+    static constexpr int n_exported_below(int a) { int n = 0; for (int b = 1; b < a; b++) n += n_exported_hop(b); return n; }   // states of the hops before a
     // spans (C4_Span, intron.c:660-672): one per state with a loop transition, in state order (Scheduler_get_span_map)
     static constexpr int n_spans() { int n = 0; for (int k = 0; k < NT; k++) n += is_span(k); return n; }
     static constexpr int span_loop(int i) { int n = 0; for (int s = 0; s < NS; s++) for (int k = 0; k < NT; k++) if (is_span(k) && M::tr[k].in == s) { if (n == i) return k; n++; } return -1; }
@@ -166,11 +174,12 @@ struct Plan {
     static constexpr bool consumes(int k) { return M::tr[k].dst_shadow_mask != 0; }
     // positions the calcs read
     static constexpr int match_at() { return Facts<M>::match_at(); }
+    static constexpr int match_aq() { return Facts<M>::match_aq(); }
     static constexpr int splice_at() { for (int k = 0; k < NT; k++) if (M::tr[k].calc >= 0 && (M::calc[M::tr[k].calc].kind == CALC_SPLICE_PRE || M::calc[M::tr[k].calc].kind == CALC_SPLICE_POST)) return M::tr[k].at; return 0; }
     static constexpr bool splice_at_ok() { for (int k = 0; k < NT; k++) if (M::tr[k].calc >= 0 && (M::calc[M::tr[k].calc].kind == CALC_SPLICE_PRE || M::calc[M::tr[k].calc].kind == CALC_SPLICE_POST) && M::tr[k].at != splice_at()) return false; return true; }
     static_assert(splice_at_ok(), "one target advance for all splice transitions");
     static constexpr bool uses_ss(int p) { for (int c = 0; c < M::NC; c++) if ((M::calc[c].kind == CALC_SPLICE_PRE || M::calc[c].kind == CALC_SPLICE_POST) && M::calc[c].param == p) return true; return false; }
-    static constexpr bool has_match() { for (int c = 0; c < M::NC; c++) if (M::calc[c].kind >= CALC_MATCH_DNA && M::calc[c].kind <= CALC_MATCH_P2D) return true; return false; }
+    static constexpr bool has_match() { for (int c = 0; c < M::NC; c++) if (calc_is_match(M::calc[c].kind)) return true; return false; }
 };
 
 template <int NS>
@@ -190,7 +199,10 @@ struct Layout {
     static constexpr int RECW = TB ? PTW + NSP : 1;          // ints per lane in a step record
     static constexpr int REC_BYTES = REC_HEAD + 256 * RECW, RPC_LOG = per_chunk_log(REC_BYTES);
     static constexpr int CW = 3 + (SH ? 1 : 0);              // ints per carried state
-    static constexpr int CENT_INTS = 2 + P::n_exported() * CW, CENT_BYTES = 4 * CENT_INTS, CPC_LOG = per_chunk_log(CENT_BYTES);
+    static constexpr int NCAR = P::n_exported_below(M::MAXAQ + 1);   // carried states: the exported ones of every hop, hop 1 first
+    static_assert(M::MAXAQ > 1 || NCAR == P::n_exported(), "one hop: the carried states are the exported ones");
+    static_assert(!BND || M::MAXAQ == 1, "the boundary flavour exchanges one query row per step");
+    static constexpr int CENT_INTS = 2 + NCAR * CW, CENT_BYTES = 4 * CENT_INTS, CPC_LOG = per_chunk_log(CENT_BYTES);
     static constexpr int ST_REC = FWD ? ST_FWDREC : ST_REVREC, ST_CARRY = FWD ? ST_FWDCARRY : ST_REVCARRY;
 };
 
@@ -222,7 +234,7 @@ struct Eval {
 
     // CBF(fire, seed id, score, transition id): an assignment into the call-back state that is a maximum of its path
     template <class CBF>
-    SDP_HD static void cell(C &cur, const C (&own)[M::MAXAT + 1], const C (&up)[M::MAXAT + 2], SpanCache (&cache)[NSPA],
+    SDP_HD static void cell(C &cur, const C (&own)[M::MAXAT + 1], const C (&up)[M::MAXAQ * (M::MAXAT + 2)], SpanCache (&cache)[NSPA],
                             const In &in, Out &out, const KParams *kp, CBF &&cbf) {
         int pt[NS];
         sfor<NS>([&](auto S_) { constexpr int S = S_; cur.sc[S] = LOW; cur.mx[S] = 0; cur.sd[S] = 0; cur.sh[S] = 0; pt[S] = 0; });
@@ -242,7 +254,7 @@ struct Eval {
             else if constexpr (t.calc >= 0) {
                 constexpr CalcDesc cd = M::calc[t.calc];
                 if constexpr (cd.kind == CALC_CONST) tscore = in.cv[t.calc];
-                else if constexpr (cd.kind >= CALC_MATCH_DNA && cd.kind <= CALC_MATCH_P2D) tscore = in.mscore;
+                else if constexpr (calc_is_match(cd.kind)) tscore = in.mscore;
                 else if constexpr (cd.kind == CALC_SPLICE_PRE) tscore = in.cv[t.calc] + in.tv.ss[cd.param];
                 else if constexpr (cd.kind == CALC_SPLICE_POST) {                  // Intron_calc_*, post (intron.c:150-160)
                     const int len = sv - s_sh + 2;
@@ -283,7 +295,7 @@ struct Eval {
             constexpr int k = P::ADV.id[I_];
             constexpr TrDesc t = M::tr[k];
             constexpr int S = P::src(k);
-            const C &s = t.aq ? up[t.at + 1] : own[t.at];
+            const C &s = t.aq ? up[(t.aq - 1) * (M::MAXAT + 2) + t.at + 1] : own[t.at];   // hop aq's ring / the lane's own
             arrive(KI<k>{}, s.sc[S], s.mx[S], s.sd[S], s.sh[S], v - t.at);
         });
         // the pointers as the advancing arrivals left them; then the cell's own sweep, one bit per static transition that assigned
@@ -475,7 +487,14 @@ struct WaveSweep {
     using L = Layout<M, FWD, BND>;
     using E = Eval<M, FWD, BND>;
     using C = SCell<M::NS>;
-    static constexpr int NS = M::NS, NEXP = P::n_exported();
+    static constexpr int NS = M::NS, NEXP = L::NCAR;
+    static constexpr int RING = M::MAXAT + 2;                      // entries of one hop's ring in up[]
+    // A strip jumps to its next event once nothing in the rings can still be a source.  A transition (aq, at) into a cell
+    // of step c reads a cell of step c - aq - at, so the oldest entry a ring hands to a cell is MAXAQ + MAXAT steps old:
+    // after that many steps without a live cell every source a later step could read is dead, and so is every cell whose
+    // entry in the carried list is still to be written (at most MAXAQ - 1 steps late, below).  One step more is waited
+    // for, as the one-hop form always did (MAXAT + 1 there): the rings are not cleared by a jump, they age out.
+    static constexpr int DEAD_RUN = M::MAXAQ + M::MAXAT;
 
     __device__ __forceinline__ static int rfl(int x) { return __builtin_amdgcn_readfirstlane(x); }
 
@@ -547,15 +566,15 @@ struct WaveSweep {
             if (lane == 0) { dir_rec[strip] = rec_count; dir_carry[strip] = carry_count; }
             const int u = ubase0 + 64 * strip + lane;
             const bool row_ok = (u >= 0) & (u <= Q);
-            // the query residue the (1, x) transitions into this row consume
-            int qpos = FWD ? u - 1 : Q - u;
+            // the query residue (codon) the match into this row consumes: it starts match_aq() rows above
+            int qpos = FWD ? u - P::match_aq() : Q - u;
             qpos = qpos < 0 ? 0 : (qpos > Q - 1 ? (Q > 0 ? Q - 1 : 0) : qpos);
             const int qrow24 = 24 * (int)qc[qpos];
-            C cur, own[M::MAXAT + 1], up[M::MAXAT + 2];
+            C cur, own[M::MAXAT + 1], up[M::MAXAQ * RING];
             auto kill = [&](C &x) { sfor<NS>([&](auto S_) { constexpr int S = S_; x.sc[S] = LOW; x.mx[S] = 0; x.sd[S] = 0; x.sh[S] = 0; }); };
             kill(cur);
             sfor<M::MAXAT + 1>([&](auto I_) { kill(own[I_]); });
-            sfor<M::MAXAT + 2>([&](auto I_) { kill(up[I_]); });
+            sfor<M::MAXAQ * RING>([&](auto I_) { kill(up[I_]); });
             SpanCache cache[E::NSPA];
             sfor<E::NSPA>([&](auto I_) { cache[I_] = SpanCache{0, 0, 0, 0, 0, 0, 0}; });
             // ---- event sources ----
@@ -574,7 +593,8 @@ struct WaveSweep {
                 }
             };
             load_seed();
-            // carried row of the strip before: entries {v, -, exported states}
+            // carried rows of the strip before: entries {v, -, exported states} of column v; with MAXAQ > 1 the exported states
+            // of hop 1 (row 63), then those of hop 2 (row 62), then hop 3 (row 61), all of the same column
             int ci = 0, ci_end = 0, cin_v = SDP_NO_EVENT;
             int cin[NEXP > 0 ? NEXP * L::CW : 1];
             if (strip > 0) { ci = prev_carry_first; ci_end = carry_count; }
@@ -625,7 +645,8 @@ struct WaveSweep {
             };
 
             int c = next_event();
-            int dead_run = M::MAXAT + 2;
+            int dead_run = DEAD_RUN + 1;
+            unsigned long long alive1 = 0, alive2 = 0;         // MAXAQ > 1: the live lanes of the two steps before
             TVals tv = load_tv(c == SDP_NO_EVENT ? 0 : c);
             while (c <= T + 63) {
                 TVals tv_next = load_tv(c + 1);
@@ -633,6 +654,7 @@ struct WaveSweep {
                 const bool inside = row_ok & (v >= 0) & (v <= T);
                 // ---- rings: the cell above (lane l - 1's last cell; lane 0: the carried row), then age everything ----
                 const bool has_cin = cin_v == c;
+                if constexpr (M::MAXAQ == 1) {
                 sfor<M::MAXAT + 1>([&](auto R_) { constexpr int a = M::MAXAT + 1 - R_; if constexpr (a >= 2) up[a] = up[a - 1]; });
                 sfor<NS>([&](auto S_) { constexpr int S = S_;
                     if constexpr (P::exported(S)) {
@@ -643,6 +665,24 @@ struct WaveSweep {
                         up[1].sd[S] = dpp_shr1(o_sd, cur.sd[S]);
                         if constexpr (L::SH) { const int o_sh = has_cin ? cin[X + 3] : 0; up[1].sh[S] = dpp_shr1(o_sh, cur.sh[S]); }
                     }
+                });
+                } else
+                // Hop a holds (u - a, v) in its first entry: hop 1 is the lane above's last cell, hop a + 1 the lane above's hop a
+                // as it stood one step ago (widest hop first, so that each reads its source before that is renewed).  Lane 0
+                // takes row 64 - a of the strip before from the carried entry of its column.
+                sfor<M::MAXAQ>([&](auto H_) { constexpr int A = M::MAXAQ - H_, B = (A - 1) * RING;
+                    sfor<M::MAXAT + 1>([&](auto R_) { constexpr int a = M::MAXAT + 1 - R_; if constexpr (a >= 2) up[B + a] = up[B + a - 1]; });
+                    sfor<NS>([&](auto S_) { constexpr int S = S_;
+                        if constexpr (P::exported_hop(S, A)) {
+                            constexpr int X = (P::n_exported_below(A) + P::exported_hop_index(S, A)) * L::CW;
+                            const int o_sc = has_cin ? cin[X] : LOW, o_mx = has_cin ? cin[X + 1] : 0, o_sd = has_cin ? cin[X + 2] : 0;
+                            const C &from = A == 1 ? cur : up[A == 1 ? 0 : B - RING + 1];
+                            up[B + 1].sc[S] = dpp_shr1(o_sc, from.sc[S]);
+                            up[B + 1].mx[S] = dpp_shr1(o_mx, from.mx[S]);
+                            up[B + 1].sd[S] = dpp_shr1(o_sd, from.sd[S]);
+                            if constexpr (L::SH) { const int o_sh = has_cin ? cin[X + 3] : 0; up[B + 1].sh[S] = dpp_shr1(o_sh, from.sh[S]); }
+                        }
+                    });
                 });
                 if (has_cin) { ci++; load_carry(); dead_run = 0; }     // the carried cell ages through the ring before the next jump
                 sfor<M::MAXAT>([&](auto R_) { constexpr int a = M::MAXAT - R_; if constexpr (a >= 2) own[a] = own[a - 1]; });
@@ -690,7 +730,7 @@ struct WaveSweep {
                     } else ln[lane] = (unsigned)out.bnd;
                     rec_count++;
                     // ---- the bottom row's cell for the strip below ----
-                    if (NEXP > 0 && strip + 1 < n_strips && (alive >> 63)) {
+                    if (M::MAXAQ == 1 && NEXP > 0 && strip + 1 < n_strips && (alive >> 63)) {
                         if ((carry_count & ((1 << L::CPC_LOG) - 1)) == 0) {
                             carry_chunk = new_chunk(tab_carry, job.tab_cap[L::ST_CARRY], carry_count >> L::CPC_LOG);
                             if (!carry_chunk) { failed = true; break; }
@@ -710,9 +750,37 @@ struct WaveSweep {
                     }
                     dead_run = 0;
                 } else dead_run++;
+                if constexpr (M::MAXAQ > 1) {
+                    // ---- the last MAXAQ rows' cells of column c - 63 for the strip below: row 63's is this step's, row 62's
+                    // that lane's cell of the step before (own[1]), row 61's the one two steps ago (own[2]); one entry when
+                    // any of them lives, each lane writing its row's part
+                    const bool any_car = ((alive >> 63) | (alive1 >> 62) | (M::MAXAQ > 2 ? alive2 >> 61 : 0ull)) & 1ull;
+                    alive2 = alive1; alive1 = alive;
+                    if (NEXP > 0 && strip + 1 < n_strips && any_car) {
+                        if ((carry_count & ((1 << L::CPC_LOG) - 1)) == 0) {
+                            carry_chunk = new_chunk(tab_carry, job.tab_cap[L::ST_CARRY], carry_count >> L::CPC_LOG);
+                            if (!carry_chunk) { failed = true; break; }
+                        }
+                        int *e = reinterpret_cast<int *>(carry_chunk + (size_t)(carry_count & ((1 << L::CPC_LOG) - 1)) * L::CENT_BYTES);
+                        if (lane == 63) { e[0] = v; e[1] = 0; }
+                        sfor<M::MAXAQ>([&](auto H_) { constexpr int A = H_ + 1;
+                            if (lane == 64 - A) {
+                                const C &from = A == 1 ? cur : own[A - 1];
+                                sfor<NS>([&](auto S_) { constexpr int S = S_;
+                                    if constexpr (P::exported_hop(S, A)) {
+                                        constexpr int X = 2 + (P::n_exported_below(A) + P::exported_hop_index(S, A)) * L::CW;
+                                        e[X] = from.sc[S]; e[X + 1] = from.mx[S]; e[X + 2] = from.sd[S];
+                                        if constexpr (L::SH) e[X + 3] = from.sh[S];
+                                    }
+                                });
+                            }
+                        });
+                        carry_count++;
+                    }
+                }
                 c++;
                 tv = tv_next;
-                if (dead_run > M::MAXAT + 1) {                  // every ring entry is dead: on to the next event
+                if (dead_run > DEAD_RUN) {                  // every ring entry is dead: on to the next event
                     const int e = next_event();
                     if (e == SDP_NO_EVENT) break;
                     if (e > c) { c = e; tv = load_tv(c); }

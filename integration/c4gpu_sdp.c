@@ -13,7 +13,9 @@
  *      threshold of that call (which --bestn / --percent raise between calls: gam.c:870).
  * Thresholds, --bestn bookkeeping, ryo / vulgar printing stay the reference's.  Not taken (the reference's own function
  * runs): --refine (GAM_Result_add_alignment then blocks the REFINED alignment's cells, gam.c:663-673), --singlepass no,
- * --geneseed, pairs whose HSP sets differ in their advances, pairs that fill all 16 alignment slots of the batch and
+ * --geneseed, models with a span along the query (ner), models that advance the query by more than one row (coding2coding is
+ * taken with C4GPU_CODON_SDP=1, opt-in: sdp_wide_model_served), pairs whose HSP sets differ in their advances, pairs that fill
+ * all 16 alignment slots of the batch and
  * pairs the library reports as not served (n_out = -1: their traceback did not fit the device).  There is no size limit:
  * the device passes are sparse wavefronts that visit what the reference's scheduler visits (c4_sdp_wave.h).
  * C4GPU_SDP_HOST=1 replaces step 2 by the reference's own SDP on the host (tests of the seam without a device);
@@ -64,6 +66,35 @@ static gdouble sdp_budget_bytes(void){
 static ShimSdpPending *sdp_cur = NULL;
 static struct { long pairs, served_pairs, alignments, flushes, async_flushes; double device_ms, replay_ms, waited_ms; } sst;
 
+/* C4GPU_CODON_SDP=1 (opt-in): a model whose transitions advance the query by up to three rows is taken when its closed
+ * tables are those of the coding2coding device family, the one wide family with SDP passes (c4_sdp_wave.h: one ring of
+ * cells above per advance).  The answer is kept per SDP object: the tables do not depend on the pair. */
+static gboolean sdp_wide_model_served(GAM *gam, Comparison *comparison){
+    static GHashTable *known = NULL;               /* SDP* -> 1 (no) or 2 (yes) */
+    register gint answer;
+    register gpointer ud;
+    c4gpu_model fm, c2c;
+    c4gpu_params params;
+    if(!(shim_env("C4GPU_CODON_SDP") && atoi(shim_env("C4GPU_CODON_SDP"))))
+        return FALSE;
+    if(!known)
+        known = g_hash_table_new(g_direct_hash, g_direct_equal);
+    if((answer = GPOINTER_TO_INT(g_hash_table_lookup(known, gam->sdp))))
+        return answer == 2;
+    ud = Model_Type_create_data(gam->gas->type, comparison->query, comparison->target);
+    answer = 1;
+    if(shim_flatten_any(gam->sdp->model, ud, &fm, FALSE)){
+        shim_params(ud, &params);
+        if((c4gpu_model_get("coding2coding", C4GPU_ALPHABET_DNA, C4GPU_ALPHABET_DNA, &params, &c2c) == 0)
+        && (c4gpu_model_device_family(&fm) >= 0)
+        && (c4gpu_model_device_family(&fm) == c4gpu_model_device_family(&c2c)))
+            answer = 2;
+        }
+    Model_Type_destroy_data(gam->gas->type, ud);
+    g_hash_table_insert(known, gam->sdp, GINT_TO_POINTER(answer));
+    return answer == 2;
+    }
+
 static gboolean sdp_eligible(GAM *gam, Comparison *comparison){
     if((shim_batch_size() <= 0) || shim_env("C4GPU_SDP_OFF") || sdp_cur)
         return FALSE;
@@ -73,7 +104,8 @@ static gboolean sdp_eligible(GAM *gam, Comparison *comparison){
         return FALSE;
     if(shim_model_has_query_span(gam->sdp->model))         /* the device SDP has no spans along the query (ner) */
         return FALSE;
-    if(shim_model_has_wide_query_advance(gam->sdp->model)) /* ... and exchanges one query row per step (c4_sdp_wave.h) */
+    if(shim_model_has_wide_query_advance(gam->sdp->model)  /* ... and, unless asked (coding2coding), one query row per step */
+    && (!sdp_wide_model_served(gam, comparison)))
         return FALSE;
     if(gam->gas->refinement != GAM_Refinement_NONE)
         return FALSE;

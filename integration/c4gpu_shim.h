@@ -23,8 +23,9 @@ gboolean shim_flatten_any(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out, gboo
  * families only know spans along the target (introns), so the heuristic seams leave such a model (ner: a span on both axes,
  * ner.c:105) to the reference's own functions */
 gboolean shim_model_has_query_span(C4_Model *m);
-/* a transition that advances the query by more than one row (coding2coding, ungapped:trans): served on the exhaustive seam only,
- * the heuristic seams (SDP, BSDP, HSP extension, seeding) leave such models to the reference */
+/* a transition that advances the query by more than one row (coding2coding, ungapped:trans): served on the exhaustive seam and,
+ * coding2coding, by BSDP's derived families; the other heuristic seams (HSP extension, seeding: C4GPU_CODON_SEED=1; SDP:
+ * C4GPU_CODON_SDP=1, coding2coding only) leave such models to the reference unless asked */
 gboolean shim_model_has_wide_query_advance(C4_Model *m);
 void shim_params(Ungapped_Data *ud, c4gpu_params *p);
 /* scoring data for calls that have no model at hand (HSP seeding): Match_ArgumentSet's matrices and translation */
