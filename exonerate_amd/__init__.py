@@ -522,13 +522,16 @@ class Engine:
             _lib().c4gpu_wordtab_destroy(tab)
 
     def seed_extend(self, params, match, pairs, width, wordlen, words, emits, strings, tpos_scale, tpos_offset, tpos_modifier,
-                    seedlen, dropoff, threshold, cap=None, first_hits=None):
+                    seedlen, dropoff, threshold, cap=None, first_hits=None, mask_query=False, mask_target=False, seed_repeat=1):
         """Word scan to stored HSPs in one device call (c4gpu_seed_extend): what a fresh HSPset per pair holds after the
         seeder has walked `strings` (the target's symbol strings, walked in order).  words as for seed_scan; emits: the
         (pair, query position) of every emission.  Returns ([(walk index of the word hit, pair, [query_start, target_start,
         length, score, cobs])] in walk order, {"n_hits", "n_extended", "n_below", "n_kept"}).  cap: room for that many
         HSPs and one call only (more kept: an empty list, n_kept says how many); None: call again until they fit.
-        first_hits: a list that receives, per pair, the walk index of its first word hit or -1 (c4gpu_seed_extend_first_hits)."""
+        first_hits: a list that receives, per pair, the walk index of its first word hit or -1 (c4gpu_seed_extend_first_hits).
+        mask_query / mask_target: that side's alphabet is soft-masked (the pairs carry the residues with their case, as for
+        hsp_extend_masked; `strings` are the masked scan strings); seed_repeat: --seedrepeat.  With any of the three off its
+        default the call is c4gpu_seed_extend_opt (hspset.c:950-970,981-995), with the defaults c4gpu_seed_extend."""
         arr, keep = _pairs(pairs)
         kind = match if isinstance(match, int) else _match_kind(match)
         tab = _wordtab(self.ctx, width, wordlen, words)
@@ -543,11 +546,18 @@ class Engine:
             so = (C.c_int32 * max(1, len(strs)))(*tpos_offset)
             stats = _abi.SeedExtendStats()
             room = 1 << 12 if cap is None else cap
+            opt = bool(mask_query) or bool(mask_target) or seed_repeat != 1
             while True:
                 out = (_abi.SeedHsp * max(1, room))()
-                if _lib().c4gpu_seed_extend(self.ctx, tab, params, kind, arr, len(pairs), sp, sn, len(strs), tpos_scale, so,
-                                            tpos_modifier, seedlen, dropoff, threshold, out, room, C.byref(stats)) != 0:
-                    raise _err("c4gpu_seed_extend")
+                if not opt:
+                    rc = _lib().c4gpu_seed_extend(self.ctx, tab, params, kind, arr, len(pairs), sp, sn, len(strs), tpos_scale, so,
+                                                  tpos_modifier, seedlen, dropoff, threshold, out, room, C.byref(stats))
+                else:
+                    rc = _lib().c4gpu_seed_extend_opt(self.ctx, tab, params, kind, arr, len(pairs), sp, sn, len(strs), tpos_scale, so,
+                                                      tpos_modifier, seedlen, dropoff, threshold, int(bool(mask_query)),
+                                                      int(bool(mask_target)), seed_repeat, out, room, C.byref(stats))
+                if rc != 0:
+                    raise _err("c4gpu_seed_extend_opt" if opt else "c4gpu_seed_extend")
                 if stats.n_kept <= room or cap is not None:
                     break
                 room = stats.n_kept

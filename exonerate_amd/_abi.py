@@ -237,6 +237,10 @@ PROTOTYPES = [
     ("c4gpu_seed_extend", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_int, C.POINTER(Pair), C.c_int32,
                                     C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
                                     C.c_int32, C.c_int32, C.c_int32, C.POINTER(SeedHsp), C.c_int64, C.POINTER(SeedExtendStats)]),
+    ("c4gpu_seed_extend_opt", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_int, C.POINTER(Pair), C.c_int32,
+                                        C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                        C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                        C.POINTER(SeedHsp), C.c_int64, C.POINTER(SeedExtendStats)]),
     ("c4gpu_seed_extend_first_hits", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),
     ("c4gpu_sdp_lattice_cells", C.c_double, [C.POINTER(Hsp), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     ("c4gpu_sdp_batch", C.c_int, [C.c_void_p, C.POINTER(Model), C.POINTER(Params), C.POINTER(Pair), C.c_int32, C.POINTER(Hsp),

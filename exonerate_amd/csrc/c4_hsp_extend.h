@@ -2,7 +2,8 @@
 //
 // Depends on nothing of the engine: c4gpu.h types and plain pointers, every routine __host__ __device__ (the LDS loader at
 // the end aside), so that tests/hsp_sim.hip holds this very code to the reference's recorded HSPs without a GPU.  The
-// kernels of c4_hsp_dev.inc and seed_chain_kernel (c4_seed_dev.inc) are loops around hsp_seed_extend / hsp_horizon_step.
+// kernels of c4_hsp_dev.inc and seed_chain_kernel (c4_seed_dev.inc) are loops around hsp_seed_extend / hsp_horizon_step /
+// hsp_entry_step.
 // Residues are read through a batch's coded arrays (qcode / tcode = substitution matrix rows; for PROTEIN2DNA tcode holds
 // the row of the codon starting at each position).  Seeds of one diagonal neighbourhood read the same cache lines; the work
 // per seed is a few hundred bytes, so the kernels are latency- and not bandwidth-bound.
@@ -124,6 +125,37 @@ __host__ __device__ __forceinline__ bool hsp_horizon_step(const HspArgs &a, cons
                                  dropped);
     horizon = h->target_start + h->length * a.at;
     return true;
+}
+
+// One horizon entry with what --seedrepeat keeps beside it (:950-970): horizon[0], the counter horizon[1] and the diagonal
+// tag horizon[2] of one (section, query frame, target frame).  A fresh set's entry is {0, 0, 0}.
+struct HspEntry { int horizon, count; unsigned tag; };
+
+// HSPset_seed_hsp on one entry, seed by seed, in the reference's order (:950-995).  With seed_repeat > 1: a seed of another
+// diagonal than the entry's tag clears horizon and counter and takes the tag (compared as 32-bit patterns: Sequence.len is a
+// guint, so diag_pos + query->len is unsigned); then the horizon test; then only every seed_repeat-th seed that passed it is
+// extended (the counter starts over).  false: nothing extended (below the horizon, or held back by the counter).  Otherwise
+// *h is the HSP and `horizon` its target end, as for hsp_horizon_step.  With seed_repeat == 1 (REPEAT false: the code is not
+// there) counter and tag are never touched and this is hsp_horizon_step on e.horizon.
+template <bool MASKED, bool REPEAT>
+__host__ __device__ __forceinline__ bool hsp_entry_step_as(const HspArgs &a, const int *sm, const c4gpu_hsp_seed sd, int seed_repeat,
+                                                           HspEntry &e, c4gpu_hsp *h, int *dropped) {
+    if constexpr (REPEAT) {
+        const unsigned tag = (unsigned)sd.target_start * (unsigned)a.aq - (unsigned)sd.query_start * (unsigned)a.at +
+                             (unsigned)a.jobs[sd.pair].qlen;
+        if (e.tag != tag) { e.horizon = 0; e.count = 0; e.tag = tag; }
+        if (sd.target_start < e.horizon) return false;
+        if (++e.count < seed_repeat) return false;
+        e.count = 0;
+    }
+    return hsp_horizon_step<MASKED>(a, sm, sd, e.horizon, h, dropped);
+}
+
+template <bool MASKED>
+__host__ __device__ __forceinline__ bool hsp_entry_step(const HspArgs &a, const int *sm, const c4gpu_hsp_seed sd, int seed_repeat,
+                                                        HspEntry &e, c4gpu_hsp *h, int *dropped) {
+    return seed_repeat > 1 ? hsp_entry_step_as<MASKED, true>(a, sm, sd, seed_repeat, e, h, dropped)
+                           : hsp_entry_step_as<MASKED, false>(a, sm, sd, seed_repeat, e, h, dropped);
 }
 
 // the matrix into the block's LDS (device only: every kernel here opens with it)

@@ -142,8 +142,10 @@ __global__ __launch_bounds__(256) void seed_fill_kernel(int n, const int *__rest
 // order only through the horizon entry the seed is tested against (:939-958) and moves (:990).  So: every hit becomes a seed
 // with the number of its entry (its slot: all entries of all pairs numbered through, slot_base[pair] + (section * aq + qf) * at
 // + tf, or n_slots for a seed without one); a stable radix sort groups the walk indices by slot, walk order kept inside a slot; one
-// lane per run of equal slots replays that entry alone (hsp_horizon_step, c4_hsp_extend.h); a prefix sum over the kept
-// verdicts in walk-index order lays the kept HSPs out as HSP_store met them.
+// lane per run of equal slots replays that entry alone (hsp_entry_step, c4_hsp_extend.h); a prefix sum over the kept
+// verdicts in walk-index order lays the kept HSPs out as HSP_store met them.  c4gpu_seed_extend_opt: the same for soft-masked
+// sets (the two-stage extension, a dropped seed's masked end as its entry's horizon, :981-995) and --seedrepeat > 1 (the entry
+// also carries its counter and diagonal tag, :950-970); what an entry holds still depends on that entry's seeds alone.
 
 // the same walk with the seed and its slot in place of the hit
 __global__ __launch_bounds__(256) void seed_expand_kernel(int n, const int *__restrict__ cnt, const int *__restrict__ first,
@@ -231,25 +233,31 @@ __global__ __launch_bounds__(64) void seed_sort_scatter_kernel(const unsigned *_
 }
 
 // One lane per run of equal slots in the sorted list (a seed without a horizon entry is a run of its own): HSPset_seed_hsp
-// seed by seed on that entry alone.  verdict[k] of walk index k: 0 skipped, 1 extended and below the threshold, 2 kept.
+// seed by seed on that entry alone (hsp_entry_step, c4_hsp_extend.h).  verdict[k] of walk index k: 0 not extended (under the
+// horizon, or under REPEAT held back by the entry's counter), 1 extended and not kept (below the threshold; under MASKED also
+// a seed dropped after its forbidding round, hsps[k] then its masked end), 2 kept.  MASKED: a.qmask / a.tmask are read.
+// REPEAT: seed_repeat > 1, the entry carries its counter and diagonal tag; every seed has an entry then (refused otherwise).
+template <bool MASKED, bool REPEAT>
 __global__ void seed_chain_kernel(const HspArgs a, const c4gpu_hsp_seed *__restrict__ seeds, const unsigned *__restrict__ keys,
-                                  const int *__restrict__ order, long long n, unsigned n_slots, const int *__restrict__ submat,
-                                  uint8_t *__restrict__ verdict, c4gpu_hsp *__restrict__ hsps) {
+                                  const int *__restrict__ order, long long n, unsigned n_slots, int seed_repeat,
+                                  const int *__restrict__ submat, uint8_t *__restrict__ verdict, c4gpu_hsp *__restrict__ hsps) {
     __shared__ int sm[24 * 24];
     hsp_load_matrix(sm, submat);
     for (long long x = blockIdx.x * (long long)blockDim.x + threadIdx.x; x < n; x += (long long)gridDim.x * blockDim.x) {
         const unsigned key = keys[x];
         const bool entry = key != n_slots;
         if (entry && x > 0 && keys[x - 1] == key) continue;              // not the first of its run
-        int horizon = 0;                                                 // a fresh set's entries start at 0: no seed (their
+        HspEntry e{0, 0, 0};                                             // a fresh set's entries start at 0: no seed (their
         for (long long y = x; y < n && keys[y] == key; y++) {            // target_start >= 0) lies below, with an entry or not
             const int k = order[y];
             const c4gpu_hsp_seed sd = seeds[k];
             c4gpu_hsp h;
-            if (sd.pair < 0 || !hsp_horizon_step<false>(a, sm, sd, horizon, &h, nullptr)) verdict[k] = 0;
+            int dropped = 0;
+            if (sd.pair < 0 || !hsp_entry_step_as<MASKED, REPEAT>(a, sm, sd, seed_repeat, e, &h, MASKED ? &dropped : nullptr))
+                verdict[k] = 0;
             else {
                 hsps[k] = h;
-                verdict[k] = h.score >= a.threshold ? 2 : 1;             // HSP_store
+                verdict[k] = !dropped && h.score >= a.threshold ? 2 : 1; // HSP_store
             }
             if (!entry) break;
         }
@@ -313,6 +321,7 @@ struct c4gpu_wordtab {
     DevBuf<c4gpu_hsp> d_hsps;
     DevBuf<c4gpu_seed_hsp> d_out;
     DevBuf<HspJob> d_jobs;
+    DevBuf<uint8_t> d_qmask, d_tmask;      // c4gpu_seed_extend_opt: the soft masks of the flagged sides (softmask_kernel)
     // scratch kept between scans of one seeder (targets of similar size follow each other)
     DevBuf<uint8_t> d_sym;
     DevBuf<int> d_cnt, d_first;
@@ -444,15 +453,20 @@ extern "C" int c4gpu_wordtab_set_emissions(c4gpu_wordtab *t, const c4gpu_seed_em
     return 0;
 }
 
-extern "C" int c4gpu_seed_extend(c4gpu_ctx *ctx, c4gpu_wordtab *t, const c4gpu_params *params, int match_type,
-                                 const c4gpu_pair *pairs, int32_t n_pairs, const uint8_t *const *symbols, const int32_t *n_symbols,
-                                 int32_t n_strings, int32_t tpos_scale, const int32_t *tpos_offset, int32_t tpos_modifier,
-                                 int32_t seedlen, int32_t dropoff, int32_t threshold, c4gpu_seed_hsp *out, int64_t cap,
-                                 c4gpu_seed_extend_stats *stats) {
+extern "C" int c4gpu_seed_extend_opt(c4gpu_ctx *ctx, c4gpu_wordtab *t, const c4gpu_params *params, int match_type,
+                                     const c4gpu_pair *pairs, int32_t n_pairs, const uint8_t *const *symbols, const int32_t *n_symbols,
+                                     int32_t n_strings, int32_t tpos_scale, const int32_t *tpos_offset, int32_t tpos_modifier,
+                                     int32_t seedlen, int32_t dropoff, int32_t threshold, int32_t mask_query, int32_t mask_target,
+                                     int32_t seed_repeat, c4gpu_seed_hsp *out, int64_t cap, c4gpu_seed_extend_stats *stats) {
     try {
         *stats = c4gpu_seed_extend_stats{0, 0, 0, 0};
         if (hipSetDevice(ctx->device) != hipSuccess) { c4h::set_error("hipSetDevice failed"); return -1; }
         if (!hsp_match_known(match_type)) { c4h::set_error("unknown match type"); return -1; }
+        if (seed_repeat < 1) { c4h::set_error("c4gpu_seed_extend: seed_repeat below 1"); return -1; }
+        if (seed_repeat > 1 && match_type == C4GPU_MATCH_PROTEIN2DNA) {
+            c4h::set_error("c4gpu_seed_extend: seed_repeat above 1 is not served for PROTEIN2DNA (seeds without a horizon entry)");
+            return -1;
+        }
         if (!t->emits_set) { c4h::set_error("c4gpu_seed_extend: no emissions set (c4gpu_wordtab_set_emissions)"); return -1; }
         if (t->emit_max_pair >= n_pairs) { c4h::set_error("c4gpu_seed_extend: an emission names a pair outside `pairs`"); return -1; }
         if (n_pairs < 0 || n_strings < 0 || tpos_scale < 1 || seedlen < 1) { c4h::set_error("c4gpu_seed_extend: bad shape"); return -1; }
@@ -532,11 +546,30 @@ extern "C" int c4gpu_seed_extend(c4gpu_ctx *ctx, c4gpu_wordtab *t, const c4gpu_p
             hipLaunchKernelGGL(seed_sort_scatter_kernel, dim3(n_tiles), dim3(64), 0, s, t->d_keys[cur].p, t->d_vals[cur].p, N, 8 * p, n_tiles,
                                t->d_hist.p, t->d_keys[cur ^ 1].p, t->d_vals[cur ^ 1].p);
         }
+        // the masks of the flagged sides, from the raw residues the batch keeps (the 64 bytes of padding included: hsp_extend_host)
+        const bool masked = mask_query || mask_target, repeat = seed_repeat > 1;
+        const uint8_t *qmask = nullptr, *tmask = nullptr;
+        if (mask_query) {
+            const long long hq_n = seqs.total_q + 64;
+            if (t->d_qmask.alloc((size_t)hq_n)) return -1;
+            hipLaunchKernelGGL(softmask_kernel, dim3(1024), dim3(256), 0, s, seqs.qraw.p, t->d_qmask.p, hq_n, aq,
+                               match_type == C4GPU_MATCH_DNA2DNA || match_type == C4GPU_MATCH_CODON2CODON ? 'n' : 'x');
+            qmask = t->d_qmask.p;
+        }
+        if (mask_target) {
+            const long long ht_n = seqs.total_t + 64;
+            if (t->d_tmask.alloc((size_t)ht_n)) return -1;
+            hipLaunchKernelGGL(softmask_kernel, dim3(1024), dim3(256), 0, s, seqs.traw.p, t->d_tmask.p, ht_n, at,
+                               match_type == C4GPU_MATCH_PROTEIN2PROTEIN ? 'x' : 'n');
+            tmask = t->d_tmask.p;
+        }
         // 4. chains, 5. compaction
         const int chain_grid = (int)std::min<long long>((N + 63) / 64, 1 << 20);
-        const HspArgs a{seqs.qcode.p, seqs.tcode.p, nullptr, nullptr, t->d_jobs.p, aq, at, seedlen, dropoff, threshold};
-        hipLaunchKernelGGL(seed_chain_kernel, dim3(chain_grid), dim3(64), 0, s, a, t->d_seeds.p, t->d_keys[cur].p, t->d_vals[cur].p, N,
-                           (unsigned)n_slots, t->d_submat.p, t->d_verdict.p, t->d_hsps.p);
+        const HspArgs a{seqs.qcode.p, seqs.tcode.p, qmask, tmask, t->d_jobs.p, aq, at, seedlen, dropoff, threshold};
+        const auto chain_kernel = masked ? (repeat ? seed_chain_kernel<true, true> : seed_chain_kernel<true, false>)
+                                         : (repeat ? seed_chain_kernel<false, true> : seed_chain_kernel<false, false>);
+        hipLaunchKernelGGL(chain_kernel, dim3(chain_grid), dim3(64), 0, s, a, t->d_seeds.p, t->d_keys[cur].p, t->d_vals[cur].p, N,
+                           (unsigned)n_slots, seed_repeat, t->d_submat.p, t->d_verdict.p, t->d_hsps.p);
         hipLaunchKernelGGL(seed_verdict_count_kernel, dim3(n_tiles), dim3(256), 0, s, t->d_verdict.p, N, t->d_hist.p, t->d_report.p + 1);
         hipLaunchKernelGGL(seed_blockscan_kernel, dim3(1), dim3(1024), 0, s, t->d_hist.p, n_tiles, t->d_report.p + 2);
         hipLaunchKernelGGL(seed_compact_kernel, dim3(n_tiles), dim3(256), 0, s, t->d_verdict.p, N, t->d_hist.p, t->d_seeds.p, t->d_hsps.p,
@@ -557,6 +590,15 @@ extern "C" int c4gpu_seed_extend(c4gpu_ctx *ctx, c4gpu_wordtab *t, const c4gpu_p
         c4h::set_error(std::string("c4gpu_seed_extend: ") + e.what());
         return -1;
     }
+}
+
+extern "C" int c4gpu_seed_extend(c4gpu_ctx *ctx, c4gpu_wordtab *t, const c4gpu_params *params, int match_type,
+                                 const c4gpu_pair *pairs, int32_t n_pairs, const uint8_t *const *symbols, const int32_t *n_symbols,
+                                 int32_t n_strings, int32_t tpos_scale, const int32_t *tpos_offset, int32_t tpos_modifier,
+                                 int32_t seedlen, int32_t dropoff, int32_t threshold, c4gpu_seed_hsp *out, int64_t cap,
+                                 c4gpu_seed_extend_stats *stats) {
+    return c4gpu_seed_extend_opt(ctx, t, params, match_type, pairs, n_pairs, symbols, n_symbols, n_strings, tpos_scale, tpos_offset,
+                                 tpos_modifier, seedlen, dropoff, threshold, 0, 0, 1, out, cap, stats);
 }
 
 extern "C" int c4gpu_seed_extend_first_hits(c4gpu_ctx *ctx, c4gpu_wordtab *t, int64_t *first_hit, int32_t n_pairs) {

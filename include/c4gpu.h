@@ -19,6 +19,7 @@
  *   c4gpu_batch_run_regions  <->  Optimal_find_path with a region (--refine)   src/hub/gam.c:605-655
  *   c4gpu_seed_scan          <->  Seeder_add_target's automaton walk src/comparison/seeder.c:649-720,852-915
  *   c4gpu_seed_extend        <->  that walk with Seeder_WordInfo_seed and HSPset_seed_hsp behind it  seeder.c:624-647, hspset.c:933-997
+ *   c4gpu_seed_extend_opt    <->  the same for soft-masked sets and --seedrepeat  src/comparison/hspset.c:950-970,981-995
  *   c4gpu_sdp_batch          <->  GAM_Result_SDP_create's loop (SDP_Pair_next_path) src/hub/gam.c:852-890, src/sdp/sdp.c:743
  */
 #ifndef INCLUDED_C4GPU_H
@@ -526,7 +527,7 @@ void        c4gpu_wordtab_stats(const c4gpu_wordtab *t, double *scan_ms, int64_t
 /* Word scan to stored HSPs in one call, the hits staying on the device: what one fresh HSPset per pair holds after
  * Seeder_add_target (seeder.c:852-915) has walked the target -- Seeder_WordInfo_seed (seeder.c:624-647) handing every hit to
  * HSPset_seed_hsp (hspset.c:933-997: horizon test :939-958, extension, HSP_store's threshold, horizon update :990), for
- * seed_repeat 1 and sets without soft-masking (those keep c4gpu_hsp_extend_*_masked).
+ * seed_repeat 1 and sets without soft-masking (c4gpu_seed_extend_opt, below, serves those).
  * c4gpu_wordtab_set_emissions tells the table what its emissions are: emission e seeds the HSPset of pairs[emits[e].pair]
  * at query position emits[e].query_pos (n_emits = emit_first[n_words] of the table).
  * c4gpu_seed_extend walks `n_strings` symbol strings in order (one target, or its three translated frames), each as
@@ -561,6 +562,29 @@ int         c4gpu_seed_extend(c4gpu_ctx *ctx, c4gpu_wordtab *t, const c4gpu_para
                               int32_t tpos_scale, const int32_t *tpos_offset, int32_t tpos_modifier,
                               int32_t seedlen, int32_t dropoff, int32_t threshold,
                               c4gpu_seed_hsp *out, int64_t cap, c4gpu_seed_extend_stats *stats);
+/* The same call for soft-masked sets and --seedrepeat (hspset.c:950-970,981-995); c4gpu_seed_extend is this call with
+ * (mask_query, mask_target, seed_repeat) = (0, 0, 1), the same kernels and results bit for bit.
+ * mask_query / mask_target: is that side's alphabet soft-masked, read exactly as by c4gpu_hsp_extend_*_masked above (the pairs
+ * carry the residues WITH their case; the symbol strings are what the seeder scans, already Sequence_mask'ed by the caller).
+ * With either flag set every extended seed takes the two-stage rule: a seed below `threshold` after the forbidding round is
+ * DROPPED -- nothing kept, and its entry becomes the target end of the masked-extended HSP (hspset.c:985-989), so a later
+ * seed of that entry past the masked end is extended where the plain rule would have skipped it.
+ * seed_repeat (HSP_Param.seed_repeat, --seedrepeat) > 1: every horizon entry also carries a counter and a diagonal tag
+ * (horizon[1] / horizon[2], hspset.c:950-970).  In the reference's order: a seed whose (uint32)(target_start * aq -
+ * query_start * at + qlen) differs from the entry's tag clears the entry's horizon and counter and takes the tag; then the
+ * horizon test; then the counter: only every seed_repeat-th seed that passed the test is extended, the others return.
+ * stats: n_extended counts the extensions that ran (a seed held back by the counter is not one); n_below = n_extended -
+ * n_kept, the dropped seeds among them.  c4gpu_seed_extend_first_hits serves this call too.
+ * Fails (-1) like c4gpu_seed_extend, and before anything is launched: seed_repeat < 1; seed_repeat > 1 with
+ * C4GPU_MATCH_PROTEIN2DNA (its seeds more than a query length above the main diagonal have a negative section: the reference
+ * indexes -- under a repeat also writes -- outside its horizon array there, so nothing defines the result). */
+int         c4gpu_seed_extend_opt(c4gpu_ctx *ctx, c4gpu_wordtab *t, const c4gpu_params *params, int match_type,
+                                  const c4gpu_pair *pairs, int32_t n_pairs,
+                                  const uint8_t *const *symbols, const int32_t *n_symbols, int32_t n_strings,
+                                  int32_t tpos_scale, const int32_t *tpos_offset, int32_t tpos_modifier,
+                                  int32_t seedlen, int32_t dropoff, int32_t threshold,
+                                  int32_t mask_query, int32_t mask_target, int32_t seed_repeat,
+                                  c4gpu_seed_hsp *out, int64_t cap, c4gpu_seed_extend_stats *stats);
 /* first_hit[p]: the walk index of pair p's FIRST word hit in the last c4gpu_seed_extend call on this table (kept or not), -1:
  * the pair had none.  Seeder_WordInfo_seed creates a query's Comparison at its first hit (seeder.c:634-640) and the report
  * loop of Seeder_add_target (seeder.c:899-913) follows that order: a caller that reports per pair needs it.  n_pairs: that

@@ -20,9 +20,10 @@
  * (opt-in) -- a seeder with a translated query (ungapped:trans, coding2coding: the words of the query's three frames in one
  * automaton, their seeds' query positions nucleotide positions already, seeder.c:540-545; the table reads them as they are).
  * C4GPU_SEED_FUSED=1 (opt-in): where every emission of the table belongs to one loader whose HSP_Param
- * the seeding seam would take (a horizon, seed_repeat 1, DNA / protein / protein-vs-DNA -- with C4GPU_CODON_SEED=1 also
- * codon-vs-codon without an annotated query --, no soft-masked alphabet) step 2 is ONE
- * c4gpu_seed_extend call per target -- scan, horizon test, extension and threshold on the device, the hits never leaving it --
+ * uses a horizon (DNA / protein / protein-vs-DNA -- with C4GPU_CODON_SEED=1 also codon-vs-codon without an annotated query --,
+ * with C4GPU_SEED_FUSED_OPT=1 beside it also soft-masked alphabets, and --seedrepeat > 1 where query and target advance are equal,
+ * so not protein-vs-DNA) step 2 is ONE
+ * c4gpu_seed_extend_opt call per target -- scan, horizon test, extension and threshold on the device, the hits never leaving it --
  * and only the HSPs a fresh HSPset per query would store come back, in walk order; each goes to HSPset_add_known_hsp of its
  * query's set; the Comparisons are created in the order of the queries' first word hits (c4gpu_seed_extend_first_hits), which is
  * the order Seeder_WordInfo_seed creates them in and the report loop follows.  A query whose hits all fall away gets no
@@ -431,6 +432,15 @@ static gint seed_match_kind(HSP_Param *param){
         }
     }
 
+/* C4GPU_SEED_FUSED_OPT=1 (opt-in, beside C4GPU_SEED_FUSED=1): the route also takes soft-masked alphabets and --seedrepeat > 1
+ * (c4gpu_seed_extend_opt); without it such runs keep the scan and extension calls, as they did before that call existed */
+static gboolean seed_fused_opt(void){
+    static gint on = -1;
+    if(on < 0)
+        on = (shim_env("C4GPU_SEED_FUSED_OPT") && atoi(shim_env("C4GPU_SEED_FUSED_OPT"))) ? 1 : 0;
+    return on ? TRUE : FALSE;
+    }
+
 /* once per table: one loader behind every emission, its HSP_Param one the seeding seam takes (hsp_eligible, c4gpu_hsp.c) */
 static void seed_fused_look(ShimSeedTab *st){
     register Seeder *seeder = st->seeder;
@@ -447,7 +457,12 @@ static void seed_fused_look(ShimSeedTab *st){
             return;
         loader = e->loader;
         }
-    if((!loader->hsp_param->use_horizon) || (loader->hsp_param->seed_repeat > 1) || (seed_match_kind(loader->hsp_param) < 0))
+    if((!loader->hsp_param->use_horizon) || (seed_match_kind(loader->hsp_param) < 0))
+        return;
+    /* --seedrepeat > 1: only where every seed has a horizon entry -- equal advances; protein against DNA keeps the other route
+     * (c4gpu_seed_extend_opt refuses it: the reference leaves its horizon array there) */
+    if((loader->hsp_param->seed_repeat > 1)
+    && ((!seed_fused_opt()) || (loader->hsp_param->match->query->advance != loader->hsp_param->match->target->advance)))
         return;
     codon = (loader->hsp_param->match->type == Match_Type_CODON2CODON);
     index = g_hash_table_new(g_direct_hash, g_direct_equal);
@@ -457,7 +472,7 @@ static void seed_fused_look(ShimSeedTab *st){
         g_hash_table_insert(index, query_info, GINT_TO_POINTER(k + 1));
         st->fused_query[k] = Sequence_get_str(query_info->query);
         /* (an annotated query of a codon loader: its sets keep the reference's function, hsp_match_kind in c4gpu_hsp.c) */
-        if(query_info->query->alphabet->is_soft_masked || (codon && query_info->query->annotation))
+        if((codon && query_info->query->annotation) || (query_info->query->alphabet->is_soft_masked && !seed_fused_opt()))
             loader = NULL;
         }
     st->fused_emits = g_new(c4gpu_seed_emit, st->emits->len);
@@ -483,10 +498,12 @@ static gboolean seed_fused_wanted(ShimSeedTab *st, Sequence *target){
         return FALSE;
     if(!st->fused_looked)
         seed_fused_look(st);
-    return st->fused_loader && (!target->alphabet->is_soft_masked);
+    /* (a soft-masked target with the second switch: c4gpu_seed_extend_opt takes the alphabets' flags) */
+    return st->fused_loader && (seed_fused_opt() || !target->alphabet->is_soft_masked);
     }
 
-/* the kept list on the device: one c4gpu_seed_extend call */
+/* the kept list on the device: one c4gpu_seed_extend_opt call.  The pairs hand the residues over with their case
+ * (Sequence_get_str, as the masked flush of c4gpu_hsp.c does); whether a lower-case letter masks is the alphabets' business. */
 static gboolean seed_fused_device(ShimSeedTab *st, Sequence *target, gchar *tstr, guchar **sym, gint32 *n_sym, gint n_strs,
                                   c4gpu_seed_hsp **kept, c4gpu_seed_extend_stats *stats, gint64 *first_hit){
     register Seeder *seeder = st->seeder;
@@ -496,6 +513,7 @@ static gboolean seed_fused_device(ShimSeedTab *st, Sequence *target, gchar *tstr
     static const gint32 frame_offset[3] = {0, 1, 2};
     register gboolean translated = param->match->target->is_translated;
     register gboolean ok = FALSE;
+    register gint mask_query = 0, mask_target = target->alphabet->is_soft_masked ? 1 : 0;
     gint64 cap = 1024;
     c4gpu_params params;
     if((!st->fused_sent) && (c4gpu_wordtab_set_emissions(st->tab, st->fused_emits, st->emits->len) != 0))
@@ -507,15 +525,17 @@ static gboolean seed_fused_device(ShimSeedTab *st, Sequence *target, gchar *tstr
         register Seeder_QueryInfo *query_info = seeder->query_info_list->pdata[i];
         pairs[i].query = (const uint8_t*)st->fused_query[i]; pairs[i].query_len = query_info->query->len;
         pairs[i].target = (const uint8_t*)tstr;              pairs[i].target_len = target->len;
+        if(query_info->query->alphabet->is_soft_masked)      /* (one alphabet for all queries of a run) */
+            mask_query = 1;
         }
     for(i = 0; i < n_strs; i++)
         cap += n_sym[i] / 64;
     for(;;){
         *kept = g_new(c4gpu_seed_hsp, cap + 1);
-        if(c4gpu_seed_extend(shim_get_ctx(), st->tab, &params, seed_match_kind(param), pairs, n_pairs,
-                             (const uint8_t *const *)sym, n_sym, n_strs, translated ? 3 : 1, frame_offset,
-                             st->fused_loader->tpos_modifier, param->seedlen, param->dropoff, param->threshold,
-                             *kept, cap, stats) != 0)
+        if(c4gpu_seed_extend_opt(shim_get_ctx(), st->tab, &params, seed_match_kind(param), pairs, n_pairs,
+                                 (const uint8_t *const *)sym, n_sym, n_strs, translated ? 3 : 1, frame_offset,
+                                 st->fused_loader->tpos_modifier, param->seedlen, param->dropoff, param->threshold,
+                                 mask_query, mask_target, param->seed_repeat, *kept, cap, stats) != 0)
             break;
         if(stats->n_kept <= cap){
             ok = TRUE;
@@ -572,7 +592,16 @@ static gboolean seed_fused_host(ShimSeedTab *st, Sequence *target, gchar **strs,
                 set = scratch[e->pair];
                 }
             before = set->hsp_list->len;
-            if((section_pos < 0) || (tpos >= set->horizon[0][section_pos][e->query_pos % aq][tpos % at]))
+            if(section_pos < 0)
+                stats->n_extended++;
+            else if(param->seed_repeat > 1){
+                /* the repeat rule as the set is about to apply it (hspset.c:950-970): another diagonal's tag clears the entry */
+                register gboolean same = ((guint)set->horizon[2][section_pos][e->query_pos % aq][tpos % at]
+                                          == ((guint)diag_pos + (guint)qlen));
+                if(((!same) || (tpos >= set->horizon[0][section_pos][e->query_pos % aq][tpos % at]))
+                && (((same ? set->horizon[1][section_pos][e->query_pos % aq][tpos % at] : 0) + 1) >= param->seed_repeat))
+                    stats->n_extended++;
+            } else if(tpos >= set->horizon[0][section_pos][e->query_pos % aq][tpos % at])
                 stats->n_extended++;
             HSPset_seed_hsp_cpu(set, e->query_pos, tpos);
             if(set->hsp_list->len > before){
