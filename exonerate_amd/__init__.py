@@ -43,7 +43,9 @@ class Model:
     _ALPHABETS = {"est2genome": (0, 0), "protein2dna": (1, 0), "protein2dna:bestfit": (1, 0),
                   "protein2genome": (1, 0), "protein2genome:bestfit": (1, 0),
                   # both DNA sequences translated, match advance 3/3 (ungapped.c:106-166, coding2coding.c:50-66)
-                  "ungapped:trans": (0, 0), "coding2coding": (0, 0)}
+                  "ungapped:trans": (0, 0), "coding2coding": (0, 0),
+                  # ... with target introns in three phases (coding2genome.c:53-74)
+                  "coding2genome": (0, 0)}
 
     def __init__(self, model_type, query_alphabet=None, target_alphabet=None, params=None, ner_open=None):
         """ner_open: exonerate's --neropen (model type "ner" only; None = the reference's default, -20)."""

@@ -307,6 +307,7 @@ PROTOTYPES = [
     ("c4m_phase_create", C.c_void_p, [C.POINTER(Params)]),
     ("c4m_protein2genome_create", C.c_void_p, [C.c_int, C.POINTER(Params)]),
     ("c4m_coding2coding_create", C.c_void_p, [C.POINTER(Params)]),
+    ("c4m_coding2genome_create", C.c_void_p, [C.POINTER(Params)]),
 ]
 
 _lib = None

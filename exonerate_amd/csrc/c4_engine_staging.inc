@@ -64,6 +64,7 @@ int model_family(const c4gpu_model &m) {
     if (model_matches<Coding2CodingStartDesc>(m)) return FAM_CODING2CODING_START;
     if (model_matches<Coding2CodingEndDesc>(m)) return FAM_CODING2CODING_END;
     if (model_matches<Coding2CodingJoinDesc>(m)) return FAM_CODING2CODING_JOIN;
+    if (model_matches<Coding2GenomeDesc>(m)) return FAM_CODING2GENOME;
     return -1;
 }
 
@@ -72,7 +73,11 @@ static bool family_is_p2g_span(int fam) {
 }
 // both sequences translated (Match_3_3): the query array holds codon row codes too.  The derived models of coding2coding
 // included: an engine of theirs on a coding2coding batch reads the batch's translated query codes (c4gpu_batch_viterbi_model)
-bool family_is_codon(int fam) { return fam == FAM_UNGAPPED_CODON || (fam >= FAM_CODING2CODING && fam <= FAM_CODING2CODING_JOIN); }
+// coding2genome is both a codon family and, below, an intron family: its batch gets codon row codes on both axes AND the forward
+// splice arrays, the base masks and the intron length limits
+bool family_is_codon(int fam) {
+    return fam == FAM_UNGAPPED_CODON || (fam >= FAM_CODING2CODING && fam <= FAM_CODING2CODING_JOIN) || fam == FAM_CODING2GENOME;
+}
 bool family_is_p2d(int fam) {
     return fam == FAM_UNGAPPED_P2D || fam == FAM_PROTEIN2DNA || fam == FAM_PROTEIN2GENOME ||
            (fam >= FAM_PROTEIN2DNA_START && fam <= FAM_PROTEIN2GENOME_JOIN) || family_is_p2g_span(fam) ||
@@ -81,11 +86,12 @@ bool family_is_p2d(int fam) {
 bool family_has_splice(int fam) {
     return fam == FAM_EST2GENOME || fam == FAM_PROTEIN2GENOME || (fam >= FAM_EST2GENOME_FWD_START && fam <= FAM_EST2GENOME_REV_JOIN) ||
            (fam >= FAM_PROTEIN2GENOME_START && fam <= FAM_PROTEIN2GENOME_JOIN) ||
-           (fam >= FAM_EST2GENOME_FWD_SPAN_SRC && fam <= FAM_EST2GENOME_REV_SPAN_DST) || family_is_p2g_span(fam);
+           (fam >= FAM_EST2GENOME_FWD_SPAN_SRC && fam <= FAM_EST2GENOME_REV_SPAN_DST) || family_is_p2g_span(fam) ||
+           fam == FAM_CODING2GENOME;
 }
 bool family_has_phase(int fam) {
     return fam == FAM_PROTEIN2GENOME || (fam >= FAM_PROTEIN2GENOME_START && fam <= FAM_PROTEIN2GENOME_JOIN) ||
-           family_is_p2g_span(fam);
+           family_is_p2g_span(fam) || fam == FAM_CODING2GENOME;
 }
 
 // ---- sequence preparation kernels -------------------------------------------------------------------------

@@ -722,7 +722,40 @@ struct ViewCtx {
         };
         add(padded(upper).c_str(), nullptr, padded(middle).c_str(), nullptr, padded(lower).c_str(), qpos, tpos);
     }
+    // ... and its d,d branch (alignment.c:844-895,1005-1009): both sequences DNA (coding2genome), the codon re-assembled across
+    // the intron on both axes, the inner lines with both translations, the match line the equivalence of the two residues
+    void add_split_codon_dna(int aq, int at, int qpos, int tpos) {
+        const int qsep = split_sep[split_count >> 1].first, tsep = split_sep[split_count >> 1].second;
+        const bool before = !(split_count & 1);
+        int start, qp[3], tp[3];
+        if (aq == 1 && at == 1) {
+            if (before) { start = 0; qp[0] = qpos; qp[1] = qpos + qsep; qp[2] = qpos + qsep + 1; tp[0] = tpos; tp[1] = tpos + tsep; tp[2] = tpos + tsep + 1; }
+            else { start = 2; qp[0] = qpos - qsep; qp[1] = qpos - qsep + 1; qp[2] = qpos; tp[0] = tpos - tsep; tp[1] = tpos - tsep + 1; tp[2] = tpos; }
+        } else if (aq == 2 && at == 2) {
+            if (before) { start = 0; qp[0] = qpos; qp[1] = qpos + 1; qp[2] = qpos + qsep; tp[0] = tpos; tp[1] = tpos + 1; tp[2] = tpos + tsep; }
+            else { start = 1; qp[0] = qpos - qsep; qp[1] = qpos; qp[2] = qpos + 1; tp[0] = tpos - tsep; tp[1] = tpos; tp[2] = tpos + 1; }
+        } else { failed = true; return; }
+        const int qn = (int)r->query_len, tn = (int)r->target_len;
+        for (int k = 0; k < 3; k++)
+            if (qp[k] < 0 || qp[k] >= qn || tp[k] < 0 || tp[k] >= tn) { failed = true; return; }
+        char qc[4] = {qsym(qp[0]), qsym(qp[1]), qsym(qp[2]), 0}, tc[4] = {tsym(tp[0]), tsym(tp[1]), tsym(tp[2]), 0};
+        split_count++;
+        const int n = std::max(aq, at);
+        char qs[16], ts[16], iqs[16], its[16], ms[16];
+        snprintf(qs, sizeof qs, "{%.*s}", n, qc + start);
+        snprintf(ts, sizeof ts, "{%.*s}", n, tc + start);
+        for (int k = 0; k < 3; k++) { qc[k] = (char)toupper((unsigned char)qc[k]); tc[k] = (char)toupper((unsigned char)tc[k]); }
+        const char q_aa = translate3(qc), t_aa = translate3(tc);
+        snprintf(iqs, sizeof iqs, "{%.*s}", n, tla(q_aa) + start);
+        snprintf(its, sizeof its, "{%.*s}", n, tla(t_aa) + start);
+        const char e = equiv_symbol(q_aa, t_aa);
+        const char cm[4] = {e, e, e, 0};
+        snprintf(ms, sizeof ms, "{%.*s}", n, cm + start);
+        add(qs, iqs, ms, its, ts, qpos, tpos);
+    }
     void add_split_codon(int aq, int at, int qpos, int tpos) {                            // alignment.c:817-1038, the p,d branch
+        if ((size_t)(split_count >> 1) >= split_sep.size()) { failed = true; return; }
+        if (match_kind == C4GPU_CALC_MATCH_CODON) { add_split_codon_dna(aq, at, qpos, tpos); return; }
         if (!q_prot || t_prot || (size_t)(split_count >> 1) >= split_sep.size()) { failed = true; return; }
         const int sep = split_sep[split_count >> 1].second;
         int start = -1, tp0 = 0, tp1 = 0, tp2 = 0;

@@ -28,6 +28,10 @@ enum Family { FAM_UNGAPPED = 0, FAM_AFFINE, FAM_EST2GENOME, FAM_UNGAPPED_P2D, FA
               // BSDP's derived models of coding2coding (match state 2): transitions leave START with a query advance of 1, 2
               // and 3; one-wave kernels with three rows per lane (R >= MAXAQ)
               FAM_CODING2CODING_START, FAM_CODING2CODING_END, FAM_CODING2CODING_JOIN,
+              // coding2genome (coding2genome.c:53-74): coding2coding with target introns in three phases, split codons either
+              // side.  A codon family (both axes translated) AND an intron family (splice arrays, base masks, intron length
+              // limits): the family_* tests name it, no range reaches it.  One-wave kernels, three rows per lane
+              FAM_CODING2GENOME,
               FAM_COUNT };
 
 struct LaunchArgs {

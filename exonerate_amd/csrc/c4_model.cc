@@ -692,13 +692,16 @@ c4m_model *c4m_coding2coding_create(const c4gpu_params *p) {
     return m;
 }
 
-// Phase_create(NULL, match = protein2dna, on_query = FALSE, on_target = TRUE), src/model/phase.c:354-548:
+// Phase_create(suffix, match, on_query = FALSE, on_target = TRUE), src/model/phase.c:354-548:
 // three target introns (phase 0:0, 1:2, 2:1) around split-codon states; the post-intron transitions score
-// the codon re-assembled across the intron from the shadow (phase.c:188-208).
-c4m_model *c4m_phase_create(const c4gpu_params *p) {
-    const std::string sfx = "phase-T";
+// the codon re-assembled across the intron from the shadow (phase.c:188-208).  Against a peptide (protein2genome,
+// suffix NULL) the split codon advances the target alone before the intron and takes the query residue behind it;
+// against DNA (coding2genome, suffix "target intron") both axes advance by the bases of the codon on either side
+// (phase.c:395-424).
+static c4m_model *phase_create(const char *suffix, bool against_peptide, const c4gpu_params *p) {
+    const std::string sfx = std::string("phase") + (suffix ? " " : "") + (suffix ? suffix : "") + (suffix ? " " : "") + "-T";
     c4m_model *m = c4m_model_create(sfx.c_str());
-    c4m_model_set_alphabets(m, C4GPU_ALPHABET_PROTEIN, C4GPU_ALPHABET_DNA);
+    c4m_model_set_alphabets(m, against_peptide ? C4GPU_ALPHABET_PROTEIN : C4GPU_ALPHABET_DNA, C4GPU_ALPHABET_DNA);
     c4m_model *i00 = c4m_intron_create(("0:0 " + sfx).c_str(), 1, p);
     c4m_model *i12 = c4m_intron_create(("1:2 " + sfx).c_str(), 1, p);
     c4m_model *i21 = c4m_intron_create(("2:1 " + sfx).c_str(), 1, p);
@@ -709,10 +712,12 @@ c4m_model *c4m_phase_create(const c4gpu_params *p) {
     int post1 = c4m_add_state(m, ("phase1post " + sfx).c_str());
     int pre2 = c4m_add_state(m, ("phase2pre " + sfx).c_str());
     int post2 = c4m_add_state(m, ("phase2post " + sfx).c_str());
-    // against a peptide, introns on the target: pre 0/1 and 0/2, post 1/2 and 1/1 (phase.c:400-411)
-    c4m_add_transition(m, ("(START) to phase1pre " + sfx).c_str(), C4M_START, pre1, 0, 1, -1, C4GPU_LABEL_SPLIT_CODON);
-    c4m_add_transition(m, ("(START) to phase2pre " + sfx).c_str(), C4M_START, pre2, 0, 2, -1, C4GPU_LABEL_SPLIT_CODON);
-    int t1 = c4m_add_transition(m, ("phase1post " + sfx + " to (END)").c_str(), post1, C4M_END, 1, 2, c1, C4GPU_LABEL_SPLIT_CODON);
+    // against a peptide, introns on the target: pre 0/1 and 0/2, post 1/2 and 1/1 (phase.c:400-411);
+    // against DNA: pre 1/1 and 2/2, post 2/2 and 1/1 (phase.c:415-424)
+    const int pre1_q = against_peptide ? 0 : 1, pre2_q = against_peptide ? 0 : 2, post1_q = against_peptide ? 1 : 2;
+    c4m_add_transition(m, ("(START) to phase1pre " + sfx).c_str(), C4M_START, pre1, pre1_q, 1, -1, C4GPU_LABEL_SPLIT_CODON);
+    c4m_add_transition(m, ("(START) to phase2pre " + sfx).c_str(), C4M_START, pre2, pre2_q, 2, -1, C4GPU_LABEL_SPLIT_CODON);
+    int t1 = c4m_add_transition(m, ("phase1post " + sfx + " to (END)").c_str(), post1, C4M_END, post1_q, 2, c1, C4GPU_LABEL_SPLIT_CODON);
     int t2 = c4m_add_transition(m, ("phase2post " + sfx + " to (END)").c_str(), post2, C4M_END, 1, 1, c2, C4GPU_LABEL_SPLIT_CODON);
     c4m_insert(m, i00, C4M_START, C4M_END);
     c4m_insert(m, i12, pre1, post1);
@@ -720,6 +725,23 @@ c4m_model *c4m_phase_create(const c4gpu_params *p) {
     c4m_shadow_add_dst_transition(m, 1, t1);                    // phase.c:528-532
     c4m_shadow_add_dst_transition(m, 2, t2);
     c4m_model_destroy(i00); c4m_model_destroy(i12); c4m_model_destroy(i21);
+    c4m_model_close(m);
+    return m;
+}
+
+c4m_model *c4m_phase_create(const c4gpu_params *p) { return phase_create(nullptr, true, p); }
+
+// Coding2Genome_create, src/model/coding2genome.c:53-74: coding2coding with the phase model against DNA inserted from the
+// codon match state back into it (Phase_create("target intron", match, FALSE, TRUE))
+c4m_model *c4m_coding2genome_create(const c4gpu_params *p) {
+    c4m_model *m = c4m_coding2coding_create(p);
+    if (!m) return nullptr;
+    c4m_model_rename(m, "coding2genome");
+    c4m_model_open(m);
+    const int match_state = m->tr[c4m_select_single_transition(m, C4GPU_LABEL_MATCH)].input;
+    c4m_model *phase = phase_create("target intron", false, p);
+    c4m_insert(m, phase, match_state, match_state);
+    c4m_model_destroy(phase);
     c4m_model_close(m);
     return m;
 }
@@ -804,6 +826,8 @@ static c4m_model *model_of_type(const char *type, int qa, int ta, const c4gpu_pa
         m = c4m_ungapped_create(C4M_ALPHABET_CODON, C4M_ALPHABET_CODON, params);
     else if ((t == "coding2coding" || t == "c2c") && qa == C4GPU_ALPHABET_DNA && ta == C4GPU_ALPHABET_DNA)
         m = c4m_coding2coding_create(params);
+    else if ((t == "coding2genome" || t == "c2g") && qa == C4GPU_ALPHABET_DNA && ta == C4GPU_ALPHABET_DNA)
+        m = c4m_coding2genome_create(params);
     return m;
 }
 

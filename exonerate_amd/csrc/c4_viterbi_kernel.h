@@ -321,18 +321,29 @@ struct WaveDP {
     // transition exists that does not pass through a state that re-starts the shadow (e.g. est2genome:
     // only the two intron states).  Dead slots are neither stored nor transported; cells leaving the
     // kernel carry 0 there.
+    // (The fixed point is worked out once per instantiation, into a table: the question is asked per transition, slot, row and
+    // ring phase, and the compiler's constant evaluator walked states x transitions for every one of them.)
+    struct LiveTable { bool v[M::NS][NDES > 0 ? NDES : 1]; };
+    static constexpr LiveTable live_table() {
+        LiveTable t{};
+        for (int e = 0; e < NDES; e++) {
+            bool live[M::NS] = {};
+            if (SPAN == 2) live[M::END] = true;          // the END cell leaves the kernel (cell_end_func)
+            for (int it = 0; it < M::NS; it++)
+                for (int k = 0; k < M::NT; k++) {
+                    const int in = M::tr[k].in, out = M::tr[k].out;
+                    if (F::consumed_designation(k) == e) live[in] = true;
+                    else if (!F::owns_shadow(in, e) && live[out]) live[in] = true;
+                }
+            for (int s = 0; s < M::NS; s++) t.v[s][e] = live[s];
+        }
+        return t;
+    }
+    static constexpr LiveTable LIVE = live_table();
     static constexpr bool slot_live(int s, int e) {
         if (NAUX && e == AUX) e = 0;
         if (e >= NDES) return true;
-        bool live[M::NS] = {};
-        if (SPAN == 2) live[M::END] = true;          // the END cell leaves the kernel (cell_end_func)
-        for (int it = 0; it < M::NS; it++)
-            for (int k = 0; k < M::NT; k++) {
-                const int in = M::tr[k].in, out = M::tr[k].out;
-                if (F::consumed_designation(k) == e) live[in] = true;
-                else if (!F::owns_shadow(in, e) && live[out]) live[in] = true;
-            }
-        return live[s];
+        return LIVE.v[s][e];
     }
 
     // a dumped cell row: the NS scores, then the shadow-like slots something can still read (slot_live), in (state, slot) order
@@ -378,7 +389,8 @@ struct WaveDP {
     __device__ __forceinline__ void export_cell(const C &c, int *out) const {
         out[0] = c.sc[S];
         static_for<NDES>([&](auto E_) __attribute__((always_inline)) { constexpr int E = E_;
-            out[1 + E] = slot_live(S, E) ? c.ex[S][E] : 0;
+            constexpr bool lv = slot_live(S, E);
+            out[1 + E] = lv ? c.ex[S][E] : 0;
         });
         if constexpr (MODE == MODE_REGION) {
             if constexpr (PACK) {
@@ -546,7 +558,15 @@ struct WaveDP {
                         codon = ((aux >> 4) & 15) | ((aux & 15) << 4) | (((tn4col >> (4 * nib)) & 15) << 8);
                     const int row = kp->codon_row[codon];
                     const int psc = kp->submat[qrow * 24 + row];
-                    tscore += (cis < cd.param) ? LOW : psc;
+                    if constexpr (F::match_aq() == 3) {
+                        // Phase_{1,2}_CODON2CODON_FALSE_TRUE_calc_func: the query is DNA too.  With no intron on the query its
+                        // three positions (phase.c:139-164) are the rows i-3 .. i-1 for either phase -- the codon the 3/3 match
+                        // of this cell reads, whose row code qrow is -- and Phase_calc_is_valid holds for the query as well
+                        // (phase.c:182: query_pos < phase, query_pos = q0 + i - aq): no split codon ends in rows 1 and 2
+                        tscore += ((cis < cd.param) | (q0 + i - t.aq < cd.param)) ? LOW : psc;
+                    } else {
+                        tscore += (cis < cd.param) ? LOW : psc;
+                    }
                 }
                 if constexpr (cd.protect & 2) tscore = tscore < LOW ? LOW : tscore;
                 if constexpr (cd.protect & 1) tscore = tscore > HIGH ? HIGH : tscore;
@@ -837,7 +857,8 @@ struct WaveDP {
                     int *ec = span_out_p + ((long long)(i0 + RR) * (T + 1) + j) * (1 + NDES);
                     ec[0] = col[PH][RR].sc[M::END];
                     static_for<NDES>([&](auto E_) __attribute__((always_inline)) { constexpr int E = E_;
-                        ec[1 + E] = slot_live(M::END, E) ? col[PH][RR].ex[M::END][E] : 0;
+                        constexpr bool lv = slot_live(M::END, E);
+                        ec[1 + E] = lv ? col[PH][RR].ex[M::END][E] : 0;
                     });
                 }
             });
@@ -1053,6 +1074,11 @@ struct WaveDP {
             static_for<R>([&](auto RR_) __attribute__((always_inline)) { constexpr int RR = RR_;
                 constexpr int MQ = F::match_aq();
                 const int qpos = q0 + i0 + RR - MQ;           // residue (codon start) consumed by the match move into row i
+                if constexpr (F::has_phase() && MQ == 3) {
+                    // the split-codon calc reads the same codon, and in a continuation seeded inside an open intron (rows 1 and 2
+                    // of the job, entered from its row 0) that codon starts above the job: any position of the sequence serves
+                    qcode[RR] = (qpos >= 0 && i0 + RR <= Q) ? qc[qpos] : 0;
+                } else
                 qcode[RR] = (i0 + RR >= MQ && i0 + RR <= Q) ? qc[qpos] : 0;
             });
             // registers start empty (row -1 does not exist; validity masks keep it unread)

@@ -256,7 +256,8 @@ void        c4gpu_params_set_forcegtag(c4gpu_params *params, int on);
  * "affine:overlap", "ungapped", "est2genome", "protein2dna", "protein2dna:bestfit", "protein2genome",
  * "protein2genome:bestfit", "ner" (DNA / DNA or protein / protein, NER open penalty C4GPU_NER_OPEN_DEFAULT),
  * "ungapped:trans" (Ungapped_create(CODON2CODON), named "ungapped:codon") and "coding2coding" (coding2coding.c:50-66):
- * DNA / DNA with both sequences translated, match advance 3/3, max_query_advance = 3.
+ * DNA / DNA with both sequences translated, match advance 3/3, max_query_advance = 3; "coding2genome" (coding2genome.c:53-74):
+ * coding2coding with target introns in phase 0, 1:2 and 2:1 and split codons either side (the phase model against DNA).
  * Returns 0 on success. */
 int         c4gpu_model_get(const char *model_type, int query_alphabet, int target_alphabet,
                             const c4gpu_params *params, c4gpu_model *out);

@@ -86,6 +86,7 @@ c4m_model *c4m_protein2dna_create(int scope_type, const c4gpu_params *p);       
 c4m_model *c4m_phase_create(const c4gpu_params *p);                                             /* phase.c:354 (protein query, target introns) */
 c4m_model *c4m_protein2genome_create(int scope_type, const c4gpu_params *p);                    /* protein2genome.c:44 */
 c4m_model *c4m_coding2coding_create(const c4gpu_params *p);                                     /* coding2coding.c:50 */
+c4m_model *c4m_coding2genome_create(const c4gpu_params *p);                                     /* coding2genome.c:53 */
 
 /* Affine_Model_Type, src/model/affine.h */
 enum { C4M_AFFINE_GLOBAL = 0, C4M_AFFINE_BESTFIT, C4M_AFFINE_LOCAL, C4M_AFFINE_OVERLAP };

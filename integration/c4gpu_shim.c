@@ -282,6 +282,12 @@ c4gpu_ctx *shim_ctx_nowait(void){
  * reference's functions. */
 static __thread gboolean shim_annotation_ok = FALSE;
 
+/* C4GPU_CODING2GENOME=1: serve coding2genome's exhaustive runs from its device family (off unless asked) */
+static gboolean shim_coding2genome_on(void){
+    register const gchar *e = shim_env("C4GPU_CODING2GENOME");
+    return e && (atoi(e) == 1);
+    }
+
 gboolean shim_flatten_any(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out, gboolean allow_span){
     register guint i, j;
     memset(out, 0, sizeof(*out));
@@ -351,10 +357,12 @@ gboolean shim_flatten_any(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out, gboo
             o->value = Intron_ArgumentSet_create(NULL)->intron_open_penalty;
         } else if(!strncmp(c->name, "5'ss reverse", 12)){
             o->kind = C4GPU_CALC_SPLICE_POST; o->param = C4GPU_SS5_REVERSE;
-        } else if(!strncmp(c->name, "phase1post to dst", 17)){
-            o->kind = C4GPU_CALC_PHASE_POST; o->param = 1;
-        } else if(!strncmp(c->name, "phase2post to dst", 17)){
-            o->kind = C4GPU_CALC_PHASE_POST; o->param = 2;
+        } else if((!strncmp(c->name, "phase1post to dst", 17)) || (!strncmp(c->name, "phase2post to dst", 17))){
+            /* split codons against a translated DNA query (coding2genome and what is derived from it): the device family is
+             * opt-in, C4GPU_CODING2GENOME=1; without it every call of such a model stays with the reference */
+            if(shim_model_has_wide_query_advance(m) && !shim_coding2genome_on())
+                return FALSE;
+            o->kind = C4GPU_CALC_PHASE_POST; o->param = (c->name[5] == '1') ? 1 : 2;
         } else {
             return FALSE;
             }
@@ -711,6 +719,10 @@ gpointer Bootstrapper_lookup(gchar *name){
     register Viterbi_DP_Func cpu = (Viterbi_DP_Func)Bootstrapper_lookup_cpu(name);
     /* only the Optimal (full Viterbi) functions are ours: "optimal_58_<model>_32_find_32_<mode>" */
     if((mode < 0) || strncmp(name, "optimal_58_", 11) || shim_env("C4GPU_DISABLE") || (!shim_args.use_gpu))
+        return (gpointer)cpu;
+    /* coding2genome unless asked for: the look-up answers what the reference's own would (no compiled function in the archive:
+     * Viterbi_calculate runs its interpreted loop, viterbi.c:855-859), so no call of the run comes here */
+    if((!strncmp(name, "optimal_58_coding2genome_32_", 28)) && (!shim_coding2genome_on()))
         return (gpointer)cpu;
     /* no compiled CPU function of this name (the archive was built without the model) and no device either: leave
      * the slot empty, Viterbi_calculate then runs the reference's interpreted loop (viterbi.c:855-859) */

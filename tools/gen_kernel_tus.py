@@ -9,7 +9,8 @@ FAMILIES = [("FAM_UNGAPPED", "UngappedDesc", "ungapped"), ("FAM_AFFINE", "Affine
             ("FAM_EST2GENOME", "Est2GenomeDesc", "est2genome"), ("FAM_UNGAPPED_P2D", "UngappedP2DDesc", "ungapped_p2d"),
             ("FAM_PROTEIN2DNA", "Protein2DnaDesc", "protein2dna"),
             ("FAM_PROTEIN2GENOME", "Protein2GenomeDesc", "protein2genome"), ("FAM_NER", "NerDesc", "ner"),
-            ("FAM_UNGAPPED_CODON", "UngappedCodonDesc", "ungapped_codon"), ("FAM_CODING2CODING", "Coding2CodingDesc", "coding2coding")]
+            ("FAM_UNGAPPED_CODON", "UngappedCodonDesc", "ungapped_codon"), ("FAM_CODING2CODING", "Coding2CodingDesc", "coding2coding"),
+            ("FAM_CODING2GENOME", "Coding2GenomeDesc", "coding2genome")]
 # BSDP's derived models (small CORNER-scoped DPs, thousands per pair): score and quadratic-space path only
 DERIVED = [("FAM_AFFINE_%s", "Affine%sDesc", "affine_%s"), ("FAM_EST2GENOME_FWD_%s", "Est2GenomeFwd%sDesc", "est2genome_fwd_%s"),
            ("FAM_EST2GENOME_REV_%s", "Est2GenomeRev%sDesc", "est2genome_rev_%s"),
@@ -34,7 +35,11 @@ VARIANTS = [("MODE_SCORE", 0, 1, 0), ("MODE_SCORE", 0, 0, 0), ("MODE_REGION", 0,
 # rows per lane: the region/checkpoint passes carry 2-3 extra ints per state, so they get fewer rows
 R = {("est2genome", "MODE_REGION"): 4, ("est2genome", "MODE_CKPT"): 3, ("est2genome", "MODE_PATH"): 1, ("protein2dna", "MODE_REGION"): 2,
      ("protein2dna", "MODE_CKPT"): 2, ("protein2genome", "MODE_SCORE"): 2, ("protein2genome", "MODE_REGION"): 2,
-     ("protein2genome", "MODE_PATH"): 2, ("protein2genome", "MODE_CKPT"): 2}
+     ("protein2genome", "MODE_PATH"): 2, ("protein2genome", "MODE_CKPT"): 2,
+     # coding2genome: 14 states with a shadow and a base slot, and a lane holds at least MAXAQ = 3 rows: three everywhere
+     # (profiles/coding2genome.md has the registers and the scratch of every form)
+     ("coding2genome", "MODE_SCORE"): 3, ("coding2genome", "MODE_REGION"): 3, ("coding2genome", "MODE_PATH"): 3,
+     ("coding2genome", "MODE_CKPT"): 3}
 # waves per SIMD the register allocator is held to (measured: est2genome region R=4 at 2 waves/SIMD beats
 # R=2/3 uncapped and R=4 at 1 wave/SIMD, profiles/r01_variants.md)
 # est2genome FIND_SCORE: 174 registers uncapped (185 with the column dumps) = 2 waves/SIMD; held to 168 it runs 3 (a
@@ -60,11 +65,11 @@ SEED2_R2 = {}
 # ONE-wave score / region kernels of these families are built all the same: they serve parameters too large for the local-scope
 # shortcuts, Engine::local_exact.  coding2coding has no cooperating-wave kernels at all yet, see ONE_WAVE_ONLY: it is listed so
 # that it is right the day that form handles a query advance of 3.)
-ONLY_LOCAL = {"est2genome", "ner", "coding2coding"}
+ONLY_LOCAL = {"est2genome", "ner", "coding2coding", "coding2genome"}       # (coding2genome.c:54: built on coding2coding)
 # families whose match advances the query by three rows (MAXAQ = 3): the one-wave kernels only -- the cooperating-wave form
 # (and the packed and seeded forms behind it) exchanges exactly one row per step and keeps its static_assert.  (ungapped_codon
 # would be left out by its name as well, like the other ungapped families; it is listed for what it is.)
-ONE_WAVE_ONLY = {"ungapped_codon", "coding2coding"}
+ONE_WAVE_ONLY = {"ungapped_codon", "coding2coding", "coding2genome"}
 
 os.makedirs(OUT, exist_ok=True)
 _written = set()
