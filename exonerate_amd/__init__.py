@@ -473,7 +473,8 @@ class Engine:
         the list of alignments found from its HSPs ([query_start, target_start, length, score, cobs] each), both
         Scheduler passes on the device (c4gpu_sdp_batch: one sparse wavefront per pair, both SDP flavours).  Served
         models: affine, protein2dna, coding2coding (seeded flavour; coding2coding with query advances up to 3, HSPs of
-        either its DNA set, advances 1/1, or its codon set, 3/3), est2genome, protein2genome (boundary flavour); any
+        either its DNA set, advances 1/1, or its codon set, 3/3), est2genome, protein2genome, coding2genome (boundary flavour;
+        coding2genome with query advances up to 3 and HSPs of either set, as coding2coding); any
         other raises C4GpuError.  A pair the device could not serve (its traceback did not fit the device's memory)
         yields None."""
         arr, keep = _pairs(pairs)

@@ -17,6 +17,7 @@ const SdpFamilyInfo *sdp_family_info(int family, const SdpKernels **k) {
         case FAM_EST2GENOME: { static const SdpFamilyInfo f = make_family_info<Est2GenomeDesc, true>(); *k = sdp_kernels_est2genome(); return &f; }
         case FAM_PROTEIN2GENOME: { static const SdpFamilyInfo f = make_family_info<Protein2GenomeDesc, true>(); *k = sdp_kernels_protein2genome(); return &f; }
         case FAM_CODING2CODING: { static const SdpFamilyInfo f = make_family_info<Coding2CodingDesc, false>(); *k = sdp_kernels_coding2coding(); return &f; }
+        case FAM_CODING2GENOME: { static const SdpFamilyInfo f = make_family_info<Coding2GenomeDesc, true>(); *k = sdp_kernels_coding2genome(); return &f; }
         default: return nullptr;                   // ungapped:trans has no SDP in the reference; ner's spans run along the query
     }
 }

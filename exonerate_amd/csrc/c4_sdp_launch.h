@@ -14,6 +14,7 @@ const SdpKernels *sdp_kernels_protein2dna();
 const SdpKernels *sdp_kernels_est2genome();
 const SdpKernels *sdp_kernels_protein2genome();
 const SdpKernels *sdp_kernels_coding2coding();
+const SdpKernels *sdp_kernels_coding2genome();
 
 #define C4SDP_DEFINE_KERNELS(SYMBOL, M, BND)                                                                           \
     static hipError_t SYMBOL##_rev(const SdpLaunch &a, int n, hipStream_t s) {                                         \

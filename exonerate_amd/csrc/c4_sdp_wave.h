@@ -4,7 +4,8 @@
 //
 // What it computes: both passes of Scheduler_Pair_calculate (scheduler.c:1445-1500) with the cell function
 // Scheduler_Cell_process (scheduler.c:859-1065) in the reference's candidate order, for both flavours of SDP_create
-// (sdp.c:322-366): bidirectional from the seeds (affine, protein2dna) and boundary + spans (est2genome, protein2genome).
+// (sdp.c:322-366): bidirectional from the seeds (affine, protein2dna, coding2coding) and boundary + spans (est2genome,
+// protein2genome, coding2genome).
 // The recurrence, its pruning rules and the traceback record are those of the dense sweep this file replaces (round 2's
 // c4_sdp.inc / c4_sdp_bnd.inc, proven against 8 reference vector sets and two fuzzers); what is new is WHERE it runs:
 //
@@ -16,9 +17,14 @@
 //     advance the query by 0 or 1: the (u, v - at) sources sit in the lane's own ring of earlier cells (VGPRs), the
 //     (u - 1, v - at) sources in the ring of the lane above, fetched once per step with DPP wave_shr:1.  Lane 0's upper
 //     neighbour is the bottom row of the strip before, which that strip left behind as a sparse list of live cells.
-//     A model whose transitions advance the query by up to 3 (coding2coding: seeded flavour only) keeps one such ring per
-//     advance ("hop"): hop a + 1 is the lane above's hop a of the step before, again one wave_shr:1, and holds (u - a - 1, v).
-//     The strip before then leaves its last MAXAQ rows behind, the cells of one column in one entry of the list.
+//     A model whose transitions advance the query by up to 3 (coding2coding: seeded flavour; coding2genome: boundary flavour)
+//     keeps one such ring per advance ("hop"): hop a + 1 is the lane above's hop a of the step before, again one wave_shr:1, and
+//     holds (u - a - 1, v).  The strip before then leaves its last MAXAQ rows behind, the cells of one column in one entry of
+//     the list.  In the forward pass of the boundary flavour every hop carries the state's shadow word with it (coding2genome:
+//     phase1post leaves over hop 2, phase2post over hop 1, each scoring with the intron start its shadow holds), the strips
+//     are anchored at the query's end, so hops cross from one strip to the next at rows that are no multiples of 64, and a
+//     boundary cell starts its state in whichever lane it falls, hop rings or not.  Spans stay what they are below: the ways
+//     out of coding2genome's three span states advance the target only.
 //   * A strip's sweep is event driven: it starts at the first step that holds a seed, a boundary cell or a live cell of
 //     the carried row, runs while anything in the rings is alive, and jumps to the next event when everything is dead.
 //     Steps in which no cell is alive leave nothing behind.  The work is the reference's own (cells inside the X-drop),
@@ -201,7 +207,6 @@ struct Layout {
     static constexpr int CW = 3 + (SH ? 1 : 0);              // ints per carried state
     static constexpr int NCAR = P::n_exported_below(M::MAXAQ + 1);   // carried states: the exported ones of every hop, hop 1 first
     static_assert(M::MAXAQ > 1 || NCAR == P::n_exported(), "one hop: the carried states are the exported ones");
-    static_assert(!BND || M::MAXAQ == 1, "the boundary flavour exchanges one query row per step");
     static constexpr int CENT_INTS = 2 + NCAR * CW, CENT_BYTES = 4 * CENT_INTS, CPC_LOG = per_chunk_log(CENT_BYTES);
     static constexpr int ST_REC = FWD ? ST_FWDREC : ST_REVREC, ST_CARRY = FWD ? ST_FWDCARRY : ST_REVCARRY;
 };
@@ -261,7 +266,10 @@ struct Eval {
                     tscore = ((len < in.min_intron) | (len > in.max_intron)) ? LOW : in.tv.ss[cd.param];
                 } else if constexpr (cd.kind == CALC_PHASE_POST) {                 // phase.c:188-213 (forward only: consumes)
                     const int cis = s_sh, tpos = sv;
-                    const bool good = cis >= cd.param;
+                    bool good = cis >= cd.param;
+                    // a DNA query (coding2genome): the query side is the codon q[u-3..u-1] for both phases, the one the match
+                    // into this row consumes (qrow24); Phase_calc_is_valid (phase.c:174-186) wants it whole
+                    if constexpr (P::match_aq() > 1) good = good & (u >= P::match_aq());
                     const int c1 = good ? cis - 1 : 0, tpc = tpos < 0 ? 0 : tpos;
                     unsigned n1, n2, n3;
                     if constexpr (cd.param == 1) {

@@ -4,7 +4,7 @@
  * (src/hub/gam.c:852-890), whose loop asks SDP_Pair_next_path (src/sdp/sdp.c:743) for one alignment after the other;
  * the first call runs the two Scheduler passes (sdp.c:538-600), one pair at a time, on one core.  For both flavours of
  * SDP_create (sdp.c:322-366: bidirectional from the seeds for affine / protein2dna, BASELINE config 1; boundary + spans
- * for est2genome / protein2genome) this file
+ * for est2genome / protein2genome / coding2genome) this file
  *   1. lets the front of GAM_Result_heuristic_create (c4gpu_bsdp.c) COLLECT (gam, comparison) here instead;
  *   2. at a flush gives the HSPs of all collected pairs to c4gpu_sdp_batch: both passes of every pair in two launches,
  *      then the reference's single-pass loop over the seeds (sdp.c:776-795) inside the library;
@@ -14,8 +14,8 @@
  * Thresholds, --bestn bookkeeping, ryo / vulgar printing stay the reference's.  Not taken (the reference's own function
  * runs): --refine (GAM_Result_add_alignment then blocks the REFINED alignment's cells, gam.c:663-673), --singlepass no,
  * --geneseed, models with a span along the query (ner), models that advance the query by more than one row (coding2coding is
- * taken with C4GPU_CODON_SDP=1, opt-in: sdp_wide_model_served), pairs whose HSP sets differ in their advances, pairs that fill
- * all 16 alignment slots of the batch and
+ * taken with C4GPU_CODON_SDP=1, coding2genome with C4GPU_CODING2GENOME_SDP=1, both opt-in: sdp_wide_model_served), pairs whose
+ * HSP sets differ in their advances, pairs that fill all 16 alignment slots of the batch and
  * pairs the library reports as not served (n_out = -1: their traceback did not fit the device).  There is no size limit:
  * the device passes are sparse wavefronts that visit what the reference's scheduler visits (c4_sdp_wave.h).
  * C4GPU_SDP_HOST=1 replaces step 2 by the reference's own SDP on the host (tests of the seam without a device);
@@ -66,16 +66,32 @@ static gdouble sdp_budget_bytes(void){
 static ShimSdpPending *sdp_cur = NULL;
 static struct { long pairs, served_pairs, alignments, flushes, async_flushes; double device_ms, replay_ms, waited_ms; } sst;
 
-/* C4GPU_CODON_SDP=1 (opt-in): a model whose transitions advance the query by up to three rows is taken when its closed
- * tables are those of the coding2coding device family, the one wide family with SDP passes (c4_sdp_wave.h: one ring of
- * cells above per advance).  The answer is kept per SDP object: the tables do not depend on the pair. */
+/* A model whose transitions advance the query by up to three rows is taken when its closed tables are those of a wide device
+ * family with SDP passes (c4_sdp_wave.h: one ring of cells above per advance) AND that family's opt-in switch is set:
+ * C4GPU_CODON_SDP=1 for coding2coding (the seeded flavour), C4GPU_CODING2GENOME_SDP=1 for coding2genome (the boundary
+ * flavour).  Either switch means its own family alone.  The answer is kept per SDP object: the tables do not depend on the
+ * pair. */
+static gboolean sdp_coding2genome_on(void){
+    return shim_env("C4GPU_CODING2GENOME_SDP") && atoi(shim_env("C4GPU_CODING2GENOME_SDP"));
+    }
+/* the seam's flattening: with coding2genome's switch the split-codon calcs of a DNA query pass */
+static gboolean sdp_flatten(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out){
+    return sdp_coding2genome_on() ? shim_flatten_split_codon(m, ud, out) : shim_flatten_any(m, ud, out, FALSE);
+    }
+
 static gboolean sdp_wide_model_served(GAM *gam, Comparison *comparison){
     static GHashTable *known = NULL;               /* SDP* -> 1 (no) or 2 (yes) */
-    register gint answer;
+    static const struct { const char *name, *env; } wide[2] = {
+        {"coding2coding", "C4GPU_CODON_SDP"}, {"coding2genome", "C4GPU_CODING2GENOME_SDP"}};
+    register gint answer, w;
     register gpointer ud;
-    c4gpu_model fm, c2c;
+    gboolean asked = FALSE;
+    c4gpu_model fm, served;
     c4gpu_params params;
-    if(!(shim_env("C4GPU_CODON_SDP") && atoi(shim_env("C4GPU_CODON_SDP"))))
+    for(w = 0; w < 2; w++)
+        if(shim_env(wide[w].env) && atoi(shim_env(wide[w].env)))
+            asked = TRUE;
+    if(!asked)
         return FALSE;
     if(!known)
         known = g_hash_table_new(g_direct_hash, g_direct_equal);
@@ -83,12 +99,14 @@ static gboolean sdp_wide_model_served(GAM *gam, Comparison *comparison){
         return answer == 2;
     ud = Model_Type_create_data(gam->gas->type, comparison->query, comparison->target);
     answer = 1;
-    if(shim_flatten_any(gam->sdp->model, ud, &fm, FALSE)){
+    if(sdp_flatten(gam->sdp->model, ud, &fm)){
         shim_params(ud, &params);
-        if((c4gpu_model_get("coding2coding", C4GPU_ALPHABET_DNA, C4GPU_ALPHABET_DNA, &params, &c2c) == 0)
-        && (c4gpu_model_device_family(&fm) >= 0)
-        && (c4gpu_model_device_family(&fm) == c4gpu_model_device_family(&c2c)))
-            answer = 2;
+        for(w = 0; w < 2; w++)
+            if(shim_env(wide[w].env) && atoi(shim_env(wide[w].env))
+            && (c4gpu_model_get(wide[w].name, C4GPU_ALPHABET_DNA, C4GPU_ALPHABET_DNA, &params, &served) == 0)
+            && (c4gpu_model_device_family(&fm) >= 0)
+            && (c4gpu_model_device_family(&fm) == c4gpu_model_device_family(&served)))
+                answer = 2;
         }
     Model_Type_destroy_data(gam->gas->type, ud);
     g_hash_table_insert(known, gam->sdp, GINT_TO_POINTER(answer));
@@ -104,7 +122,7 @@ static gboolean sdp_eligible(GAM *gam, Comparison *comparison){
         return FALSE;
     if(shim_model_has_query_span(gam->sdp->model))         /* the device SDP has no spans along the query (ner) */
         return FALSE;
-    if(shim_model_has_wide_query_advance(gam->sdp->model)  /* ... and, unless asked (coding2coding), one query row per step */
+    if(shim_model_has_wide_query_advance(gam->sdp->model)  /* ... and, unless asked (coding2coding, coding2genome), one query row per step */
     && (!sdp_wide_model_served(gam, comparison)))
         return FALSE;
     if(gam->gas->refinement != GAM_Refinement_NONE)
@@ -293,7 +311,7 @@ static SdpFlight *sdp_flight_prepare(GPtrArray *todo){
     f->first[n] = f->hsps->len;
     p = todo->pdata[0];
     ud = Model_Type_create_data(gam->gas->type, p->comparison->query, p->comparison->target);
-    if(f->qa && shim_flatten_any(gam->sdp->model, ud, &f->fm, FALSE)){
+    if(f->qa && sdp_flatten(gam->sdp->model, ud, &f->fm)){
         shim_params(ud, &f->params);
         f->ready = TRUE;
         }

@@ -282,6 +282,10 @@ c4gpu_ctx *shim_ctx_nowait(void){
  * reference's functions. */
 static __thread gboolean shim_annotation_ok = FALSE;
 
+/* Set around the flattening of a seam that has its own switch for split codons against a translated DNA query (the SDP seam,
+ * C4GPU_CODING2GENOME_SDP=1: shim_flatten_split_codon) */
+static __thread gboolean shim_split_codon_ok = FALSE;
+
 /* C4GPU_CODING2GENOME=1: serve coding2genome's exhaustive runs from its device family (off unless asked) */
 static gboolean shim_coding2genome_on(void){
     register const gchar *e = shim_env("C4GPU_CODING2GENOME");
@@ -359,8 +363,9 @@ gboolean shim_flatten_any(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out, gboo
             o->kind = C4GPU_CALC_SPLICE_POST; o->param = C4GPU_SS5_REVERSE;
         } else if((!strncmp(c->name, "phase1post to dst", 17)) || (!strncmp(c->name, "phase2post to dst", 17))){
             /* split codons against a translated DNA query (coding2genome and what is derived from it): the device family is
-             * opt-in, C4GPU_CODING2GENOME=1; without it every call of such a model stays with the reference */
-            if(shim_model_has_wide_query_advance(m) && !shim_coding2genome_on())
+             * opt-in, C4GPU_CODING2GENOME=1 (the SDP seam: its own switch); without it every call of such a model stays with the
+             * reference */
+            if(shim_model_has_wide_query_advance(m) && (!shim_coding2genome_on()) && (!shim_split_codon_ok))
                 return FALSE;
             o->kind = C4GPU_CALC_PHASE_POST; o->param = (c->name[5] == '1') ? 1 : 2;
         } else {
@@ -413,6 +418,14 @@ gboolean shim_model_has_query_span(C4_Model *m){
             return TRUE;
         }
     return FALSE;
+    }
+
+gboolean shim_flatten_split_codon(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out){
+    register gboolean ok;
+    shim_split_codon_ok = TRUE;
+    ok = shim_flatten_any(m, ud, out, FALSE);
+    shim_split_codon_ok = FALSE;
+    return ok;
     }
 
 static gboolean shim_flatten(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out){

@@ -19,13 +19,17 @@ void shim_mark(const gchar *what);
 gint shim_batch_size(void);
 /* closed C4_Model -> c4gpu_model; allow_span: BSDP's span models (cell_start_func / cell_end_func become matrices) */
 gboolean shim_flatten_any(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out, gboolean allow_span);
+/* ... for a seam that serves split codons against a translated DNA query (coding2genome) under a switch of its own, whatever
+ * C4GPU_CODING2GENOME (the exhaustive seam's switch) says */
+gboolean shim_flatten_split_codon(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out);
 /* TRUE when some span of the model (C4_Model_add_span) loops on the query axis: the device SDP passes and BSDP's compiled span
  * families only know spans along the target (introns), so the heuristic seams leave such a model (ner: a span on both axes,
  * ner.c:105) to the reference's own functions */
 gboolean shim_model_has_query_span(C4_Model *m);
 /* a transition that advances the query by more than one row (coding2coding, ungapped:trans): served on the exhaustive seam and,
  * coding2coding, by BSDP's derived families; the other heuristic seams (HSP extension, seeding: C4GPU_CODON_SEED=1; SDP:
- * C4GPU_CODON_SDP=1, coding2coding only) leave such models to the reference unless asked */
+ * C4GPU_CODON_SDP=1 for coding2coding, C4GPU_CODING2GENOME_SDP=1 for coding2genome) leave such models to the reference unless
+ * asked */
 gboolean shim_model_has_wide_query_advance(C4_Model *m);
 void shim_params(Ungapped_Data *ud, c4gpu_params *p);
 /* scoring data for calls that have no model at hand (HSP seeding): Match_ArgumentSet's matrices and translation */
