@@ -33,9 +33,26 @@
 //       - the lineage of `unset` (-32 768 plus what a path can gain) lies in [-32768, -32768 + 16 000 + a site]: negative finite
 //         halves, which lose to every legitimate operand under either order, and a match state always has START's PK16_BIAS among
 //         its operands: the (reversed) float order among negative halves never decides a value a result reads;
-//       - an addend of exactly -32 768 (a dead row's match score, a too-short intron, --forcegtag's sentinel clamped) takes a
-//         legitimate value to <= 0x7BFF - 32768 = -1 025 = 0xFBFF, a negative finite half; a later post-splice site adds at most
+//       - an addend of exactly -32 768 (a dead row's match score, --forcegtag's sentinel clamped) takes a legitimate value to
+//         <= 0x7BFF - 32768 = -1 025 = 0xFBFF, a negative finite half; a later post-splice site adds at most
 //         PK16_POST_GAIN_MAX, which PK16_BIAS leaves room for; addends between are what the host's guard refuses;
+//       - a too-short intron (eval_cell, CALC_SPLICE_POST): the veto is the sign bits of the length counter, -32 768 in a half
+//         whose counter is negative and 0 in the others, added AFTER the site: sat(sat(src + site) + veto).  Where the counter is
+//         not negative that is src + site, bit for bit.  Where it is negative: a legitimate src is <= PK16_BIAS + PK16_SCORE_MAX and
+//         a site adds at most PK16_POST_GAIN_MAX (the guard), so src + site <= 0x7BFF without saturating (c4_pk16_bias.h's first
+//         static_assert) and the candidate is <= -1 025, a negative finite half; an src of `unset`'s lineage or of legitimate
+//         - 32 768 is negative, stays negative with a site added, and -32 768 more saturates to -32 768 = 0x8000 (-0.0, finite).
+//         Either way the candidate loses to START's PK16_BIAS in the match state it enters, as `src - 32 768` did;
+//       - the end-cell test: best_pk is one more operand of the maximum3 tree over the states that enter END, and the wave enters
+//         the bookkeeping where the tree's result differs from best_pk in any bit.  best_pk holds per half one of: real best +
+//         PK16_BIAS of a cell already recorded (legitimate, and some operand of the trees so far: a normal half); -32 768 = 0x8000
+//         for a job without an end cell yet (-0.0: finite, and below every match state, which is >= PK16_BIAS -- the tree then
+//         differs, as best_pk < m did); 0x7BFF for a lane none of whose rows belongs to the job (the largest finite half, the
+//         largest value pk16_fits admits: nothing legitimate exceeds it, and an equal one does not differ).  So no half of best_pk
+//         is a NaN pattern, and among such operands the tree returns the bit pattern of its largest operand: it differs from
+//         best_pk exactly where a state that enters END is > best_pk, the old test.  A NaN among the states (cells beyond a job's
+//         own T, next item) makes the result a NaN, which differs: the wave enters the bookkeeping, which recomputes everything
+//         per half as integers and ignores such cells (j <= T[H]) -- what it writes (best, best_i, best_j) is unchanged;
 //       - cells of the shorter job of a lane beyond its own T may exceed 16 000 where an intron can gain, and then hold a NaN:
 //         the halves of a packed instruction are independent, such cells are neither dumped nor reported (j <= T[H] in both
 //         places), and every transition advances away from the rectangle, so nothing of them comes back.  (Their half then sends
@@ -208,7 +225,8 @@ struct WaveDP16 {
     const uint8_t *tdense;                              // [24] code -> dense index (0xff: not in the launch), [24 + d] code of index d
     int best[2], best_i[2], best_j[2], best_pk;
     int unset_pk;                       // what best_pk holds for a job without an end cell yet: -32 768; IO 1, a lane none of whose rows
-                                        // belongs to the job: 32 767 (nothing of it can be an end cell, nothing beats it)
+                                        // belongs to the job: 32 767 (nothing of it can be an end cell, nothing beats it); BIAS: 0x7BFF,
+                                        // the largest finite half -- best_pk is an operand of a float maximum there
     // best_i: (query row << 4) | the state the cell's END was entered from (Roots): the row-major order of the rows is
     // that of these numbers, and no register is spent on the state
     static_assert(M::NS <= 16, "state in four bits");
@@ -369,9 +387,15 @@ struct WaveDP16 {
                     static_assert(live(t.in), "post-splice calc without a length");
                     // length so far < min - at - 2: the counter starts at -(min - at - 2) (open_il_pk), so that is its sign -- one
                     // instruction where a comparison with the limit is two
-                    const int bad = pk_neg_mask(src.il[t.in], fifteen);
-                    const int sv = (bad & NEG16) | (~bad & sp[cd.param]);
-                    cand = pk_add<VAR>(cand, sv);
+                    if constexpr (BIAS) {
+                        // the counter's sign bits ARE the veto's addend: -32 768 where the intron is too short, 0 elsewhere, added
+                        // after the site (the header's note: legitimate + site stays finite, so the sum ends <= -1 025)
+                        cand = pk_add<VAR>(pk_add<VAR>(cand, sp[cd.param]), src.il[t.in] & NEG16);
+                    } else {
+                        const int bad = pk_neg_mask(src.il[t.in], fifteen);
+                        const int sv = (bad & NEG16) | (~bad & sp[cd.param]);
+                        cand = pk_add<VAR>(cand, sv);
+                    }
                 }
             }
             if constexpr (!JINT && t.at > 0) cand = (j >= t.at) ? cand : NEG16;
@@ -447,27 +471,29 @@ struct WaveDP16 {
         });
         // end cell (viterbi.c:778-791): a new maximum is rare; one packed maximum over the lane's cells decides
         {
-            int m = 0;
+            bool cand;
             if constexpr (BIAS) {
-                // END of the lane's rows: the maximum of the states that enter it, two per instruction
-                int pend = 0, n = 0;
+                // END of the lane's rows is the maximum of the states that enter it; best_pk joins them as one more operand, two
+                // operands per instruction: the maximum differs from best_pk exactly where a cell beats it (the header's note on
+                // what best_pk may hold) -- one compare where a saturating difference and a sign test were three
+                int m = best_pk, pend = 0, n = 0;
                 static_for<R>([&](auto RR_) __attribute__((always_inline)) { constexpr int RR = RR_;
                     static_for<NS>([&](auto S_) __attribute__((always_inline)) { constexpr int S = S_;
                         if constexpr (feeds_end(S)) {
                             const int v = col[PH][RR].sc[S];
-                            if (n == 0) m = v;
-                            else if (n % 2 == 1) pend = v;
+                            if (n % 2 == 0) pend = v;
                             else m = pk_max3(m, pend, v);
                             n++;
                         }
                     });
                 });
-                if (n % 2 == 0) m = pk_max<VAR>(m, pend);
+                if (n % 2 == 1) m = pk_max3(m, pend, pend);
+                cand = m != best_pk;
             } else {
-                m = col[PH][0].sc[M::END];
+                int m = col[PH][0].sc[M::END];
                 static_for<R>([&](auto RR_) __attribute__((always_inline)) { constexpr int RR = RR_; if constexpr (RR > 0) m = pk_max<VAR>(m, col[PH][RR].sc[M::END]); });
+                cand = (pk_sub(best_pk, m) & NEG16) != 0;
             }
-            const bool cand = (pk_sub(best_pk, m) & NEG16) != 0;
             if (__builtin_amdgcn_ballot_w64(cand)) {
                 static_for<2>([&](auto H_) __attribute__((always_inline)) { constexpr int H = H_;
                     const bool jact = (j >= 0) & (j <= T[H]);
@@ -654,7 +680,8 @@ struct WaveDP16 {
             unset_pk = NEG16;
             if constexpr (IO == 1) {
                 build_profile(i0);
-                unset_pk = pk_pack(i0 > Q[0] ? 32767 : -32768, i0 > Q[1] ? 32767 : -32768);
+                constexpr int NO_ROW = BIAS ? PK16_HALF_FINITE_MAX : 32767;
+                unset_pk = pk_pack(i0 > Q[0] ? NO_ROW : -32768, i0 > Q[1] ? NO_ROW : -32768);
             } else {
                 static_for<2>([&](auto H_) __attribute__((always_inline)) { constexpr int H = H_;
                     static_for<R>([&](auto RR_) __attribute__((always_inline)) { constexpr int RR = RR_;
