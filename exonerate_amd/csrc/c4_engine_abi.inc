@@ -314,7 +314,10 @@ int c4gpu_batch_viterbi_model(c4gpu_batch *b, const c4gpu_model *model, int mode
             // the resident arrays were prepared for the batch's own model: the other model must read the same ones
             if (family_is_p2d(e->eng.family) != family_is_p2d(b->eng.family) || family_is_codon(e->eng.family) != family_is_codon(b->eng.family) ||
                 (family_has_splice(e->eng.family) && !family_has_splice(b->eng.family)) ||
-                (family_has_phase(e->eng.family) && !family_has_phase(b->eng.family))) {
+                (family_has_phase(e->eng.family) && !family_has_phase(b->eng.family)) ||
+                // the two codon models share their arrays' layout but not their derived models: coding2coding's on a
+                // coding2genome batch is a caller's mistake (the other way round fails the splice test above)
+                (family_is_coding2coding(e->eng.family) && family_is_coding2genome(b->eng.family))) {
                 c4h::set_error(std::string("model [") + model->name + "] needs sequence arrays this batch was not built with");
                 return -1;
             }

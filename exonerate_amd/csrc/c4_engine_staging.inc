@@ -65,18 +65,43 @@ int model_family(const c4gpu_model &m) {
     if (model_matches<Coding2CodingEndDesc>(m)) return FAM_CODING2CODING_END;
     if (model_matches<Coding2CodingJoinDesc>(m)) return FAM_CODING2CODING_JOIN;
     if (model_matches<Coding2GenomeDesc>(m)) return FAM_CODING2GENOME;
+    if (model_matches<Coding2GenomeStartDesc>(m)) return FAM_CODING2GENOME_START;
+    if (model_matches<Coding2GenomeEndDesc>(m)) return FAM_CODING2GENOME_END;
+    if (model_matches<Coding2GenomeJoinDesc>(m)) return FAM_CODING2GENOME_JOIN;
+    if (model_matches<Coding2GenomePhase0SpanSrcDesc>(m)) return FAM_CODING2GENOME_PHASE0_SPAN_SRC;
+    if (model_matches<Coding2GenomePhase0SpanDstDesc>(m)) return FAM_CODING2GENOME_PHASE0_SPAN_DST;
+    if (model_matches<Coding2GenomePhase1SpanSrcDesc>(m)) return FAM_CODING2GENOME_PHASE1_SPAN_SRC;
+    if (model_matches<Coding2GenomePhase1SpanDstDesc>(m)) return FAM_CODING2GENOME_PHASE1_SPAN_DST;
+    if (model_matches<Coding2GenomePhase2SpanSrcDesc>(m)) return FAM_CODING2GENOME_PHASE2_SPAN_SRC;
+    if (model_matches<Coding2GenomePhase2SpanDstDesc>(m)) return FAM_CODING2GENOME_PHASE2_SPAN_DST;
     return -1;
 }
 
 static bool family_is_p2g_span(int fam) {
     return fam >= FAM_PROTEIN2GENOME_PHASE0_SPAN_SRC && fam <= FAM_PROTEIN2GENOME_PHASE2_SPAN_DST;
 }
+// coding2genome's six span models (one src / dst pair per intron phase), named one by one
+static bool family_is_c2g_span(int fam) {
+    return fam == FAM_CODING2GENOME_PHASE0_SPAN_SRC || fam == FAM_CODING2GENOME_PHASE0_SPAN_DST ||
+           fam == FAM_CODING2GENOME_PHASE1_SPAN_SRC || fam == FAM_CODING2GENOME_PHASE1_SPAN_DST ||
+           fam == FAM_CODING2GENOME_PHASE2_SPAN_SRC || fam == FAM_CODING2GENOME_PHASE2_SPAN_DST;
+}
+// coding2genome and BSDP's nine derived models of it: codon families (the query is translated per position) that are splice and
+// phase families too (forward splice arrays, base masks, intron length limits)
+bool family_is_coding2genome(int fam) {
+    return fam == FAM_CODING2GENOME || fam == FAM_CODING2GENOME_START || fam == FAM_CODING2GENOME_END ||
+           fam == FAM_CODING2GENOME_JOIN || family_is_c2g_span(fam);
+}
+// coding2coding and its three derived models
+bool family_is_coding2coding(int fam) {
+    return fam == FAM_CODING2CODING || fam == FAM_CODING2CODING_START || fam == FAM_CODING2CODING_END || fam == FAM_CODING2CODING_JOIN;
+}
 // both sequences translated (Match_3_3): the query array holds codon row codes too.  The derived models of coding2coding
 // included: an engine of theirs on a coding2coding batch reads the batch's translated query codes (c4gpu_batch_viterbi_model)
 // coding2genome is both a codon family and, below, an intron family: its batch gets codon row codes on both axes AND the forward
 // splice arrays, the base masks and the intron length limits
 bool family_is_codon(int fam) {
-    return fam == FAM_UNGAPPED_CODON || (fam >= FAM_CODING2CODING && fam <= FAM_CODING2CODING_JOIN) || fam == FAM_CODING2GENOME;
+    return fam == FAM_UNGAPPED_CODON || (fam >= FAM_CODING2CODING && fam <= FAM_CODING2CODING_JOIN) || family_is_coding2genome(fam);
 }
 bool family_is_p2d(int fam) {
     return fam == FAM_UNGAPPED_P2D || fam == FAM_PROTEIN2DNA || fam == FAM_PROTEIN2GENOME ||
@@ -87,11 +112,11 @@ bool family_has_splice(int fam) {
     return fam == FAM_EST2GENOME || fam == FAM_PROTEIN2GENOME || (fam >= FAM_EST2GENOME_FWD_START && fam <= FAM_EST2GENOME_REV_JOIN) ||
            (fam >= FAM_PROTEIN2GENOME_START && fam <= FAM_PROTEIN2GENOME_JOIN) ||
            (fam >= FAM_EST2GENOME_FWD_SPAN_SRC && fam <= FAM_EST2GENOME_REV_SPAN_DST) || family_is_p2g_span(fam) ||
-           fam == FAM_CODING2GENOME;
+           family_is_coding2genome(fam);
 }
 bool family_has_phase(int fam) {
     return fam == FAM_PROTEIN2GENOME || (fam >= FAM_PROTEIN2GENOME_START && fam <= FAM_PROTEIN2GENOME_JOIN) ||
-           family_is_p2g_span(fam) || fam == FAM_CODING2GENOME;
+           family_is_p2g_span(fam) || family_is_coding2genome(fam);
 }
 
 // ---- sequence preparation kernels -------------------------------------------------------------------------

@@ -32,6 +32,13 @@ enum Family { FAM_UNGAPPED = 0, FAM_AFFINE, FAM_EST2GENOME, FAM_UNGAPPED_P2D, FA
               // side.  A codon family (both axes translated) AND an intron family (splice arrays, base masks, intron length
               // limits): the family_* tests name it, no range reaches it.  One-wave kernels, three rows per lane
               FAM_CODING2GENOME,
+              // BSDP's derived models of coding2genome (match state 2; span states 11, 12, 13 = intron 0:0, 1:2, 2:1): terminals,
+              // join, and a span src / dst pair per intron phase.  Codon AND intron families, like the model itself; one-wave
+              // kernels with three rows per lane, the span ones included
+              FAM_CODING2GENOME_START, FAM_CODING2GENOME_END, FAM_CODING2GENOME_JOIN,
+              FAM_CODING2GENOME_PHASE0_SPAN_SRC, FAM_CODING2GENOME_PHASE0_SPAN_DST,
+              FAM_CODING2GENOME_PHASE1_SPAN_SRC, FAM_CODING2GENOME_PHASE1_SPAN_DST,
+              FAM_CODING2GENOME_PHASE2_SPAN_SRC, FAM_CODING2GENOME_PHASE2_SPAN_DST,
               FAM_COUNT };
 
 struct LaunchArgs {

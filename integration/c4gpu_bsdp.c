@@ -75,6 +75,7 @@ typedef struct {
     GAM *gam;
     Comparison *comparison;
     GArray *sars;                  /* ShimSar, in creation order */
+    guint n_cand;                  /* the candidates of the dry run (path-only entries are appended behind them) */
     GHashTable *index;             /* (optimal, regions) -> ShimSar* */
     /* --refine: the pair's FIRST refinement (GAM_Result_refine_alignment, gam.c:605-655) is part of a batch too */
     gboolean refine_seen, refine_have, refine_used;
@@ -87,8 +88,8 @@ static gint bsdp_mode = BSDP_OFF;
 static ShimHPending *bsdp_cur = NULL;
 static GPtrArray *bsdp_pending = NULL;
 static struct { long pairs, candidates, spans, score_calls, score_served, path_calls, path_served, flushes,
-                     refine_calls, refine_served;
-                double device_ms, dry_ms, replay_ms, refine_ms; } st;
+                     refine_calls, refine_served, checked, mismatches;
+                double device_ms, dry_ms, replay_ms, refine_ms, check_ms; } st;
 
 static guint sar_hash(gconstpointer p){
     const ShimSar *s = p;
@@ -315,6 +316,19 @@ Alignment *shim_bsdp_find_path(Optimal *optimal, Region *region, SubOpt *subopt)
 typedef struct { Optimal *optimal; c4gpu_model fm; gboolean ok; GArray *members; /* (pair index, sar index) */ } ShimGroup;
 typedef struct { gint pair, sar; } ShimMember;
 
+/* C4GPU_CODING2GENOME_BSDP=1: serve coding2genome's heuristic sub-DPs -- its terminals, join and the span src / dst / src
+ * traceback models of its three intron phases -- from their device families (off unless asked; C4GPU_CODING2GENOME and
+ * C4GPU_CODING2GENOME_SDP are other seams' switches and do not turn this on) */
+static gboolean bsdp_coding2genome_on(void){
+    register const gchar *e = shim_env("C4GPU_CODING2GENOME_BSDP");
+    return e && (atoi(e) == 1);
+    }
+/* the seam's flattening: with that switch the split-codon calcs of a translated DNA query pass */
+static gboolean bsdp_flatten(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out, gboolean allow_span){
+    return bsdp_coding2genome_on() ? shim_flatten_split_codon_any(m, ud, out, allow_span)
+                                   : shim_flatten_any(m, ud, out, allow_span);
+    }
+
 static ShimGroup *bsdp_group(GPtrArray *groups, Optimal *optimal, Ungapped_Data *ud){
     register guint i;
     register ShimGroup *g;
@@ -325,7 +339,7 @@ static ShimGroup *bsdp_group(GPtrArray *groups, Optimal *optimal, Ungapped_Data 
         }
     g = g_new0(ShimGroup, 1);
     g->optimal = optimal;
-    g->ok = shim_flatten_any(optimal->find_score ? optimal->find_score->model : optimal->find_path->model, ud, &g->fm, TRUE);
+    g->ok = bsdp_flatten(optimal->find_score ? optimal->find_score->model : optimal->find_path->model, ud, &g->fm, TRUE);
     g->members = g_array_new(FALSE, FALSE, sizeof(ShimMember));
     g_ptr_array_add(groups, g);
     return g;
@@ -416,7 +430,7 @@ static void bsdp_host_scores(ShimHPending *hp){
             if(g_hash_table_lookup(seen, opts[o]))
                 continue;
             g_hash_table_insert(seen, opts[o], opts[o]);
-            if((!shim_flatten_any(m, ud, &fm, TRUE)) || (c4gpu_model_device_family(&fm) < 0))
+            if((!bsdp_flatten(m, ud, &fm, TRUE)) || (c4gpu_model_device_family(&fm) < 0))
                 g_warning("c4gpu bsdp: model [%s] has no device family", m->name);
             else if(shim_env("C4GPU_VERBOSE"))
                 g_message("c4gpu bsdp: model [%s] -> device family %d", m->name, c4gpu_model_device_family(&fm));
@@ -425,6 +439,67 @@ static void bsdp_host_scores(ShimHPending *hp){
     SubOpt_destroy(empty);
     Model_Type_destroy_data(hp->gam->gas->type, ud);
     return;
+    }
+
+/* C4GPU_BSDP_CHECK=1 (the seam's counterpart of C4GPU_HSP_CHECK / C4GPU_SEED_CHECK): every candidate the device answered is
+ * computed again by the reference's own Optimal_find_score / Optimal_find_path_cpu -- the same derived Optimal over the same
+ * regions of the same sequences, spans through Heuristic_Span_register / _integrate, exactly what host mode runs -- and
+ * compared: score, and the path (operations and region) where the device delivered one.  The only way the reference itself
+ * judges SUB-rectangles of long sequences (splice context, the bases above a region's first row).  Off: no work. */
+static gboolean bsdp_same_path(ShimSar *a, ShimSar *b){
+    return (a->n_ops == b->n_ops) && (!memcmp(a->path_region, b->path_region, sizeof(a->path_region)))
+        && ((!a->n_ops) || (!memcmp(a->ops, b->ops, sizeof(gint) * a->n_ops)));
+    }
+static void bsdp_check(ShimHPending *hp){
+    ShimHPending chk = *hp;
+    register guint i, k;
+    chk.sars = g_array_new(FALSE, TRUE, sizeof(ShimSar));
+    for(i = 0; i < hp->n_cand; i++){
+        ShimSar c = g_array_index(hp->sars, ShimSar, i);
+        c.raw = C4_IMPOSSIBLY_LOW_SCORE; c.n_ops = 0; c.ops = NULL; c.have_path = FALSE;
+        memset(c.path_region, 0, sizeof(c.path_region));
+        g_array_append_val(chk.sars, c);
+        }
+    bsdp_host_scores(&chk);
+    for(i = 0; i < chk.sars->len; i++){
+        register ShimSar *ref = &g_array_index(chk.sars, ShimSar, i), *dev = NULL;
+        register gboolean bad;
+        if(i < hp->n_cand)
+            dev = &g_array_index(hp->sars, ShimSar, i);
+        else                                    /* a src traceback: the device's entry with the same model and region */
+            for(k = hp->n_cand; (!dev) && (k < hp->sars->len); k++)
+                if(sar_equal(ref, &g_array_index(hp->sars, ShimSar, k)))
+                    dev = &g_array_index(hp->sars, ShimSar, k);
+        bad = (!dev) || (dev->raw != ref->raw) || (dev->have_path != ref->have_path)
+           || (dev->have_path && (!bsdp_same_path(dev, ref)));
+        st.checked++;
+        if(bad){
+            if((!st.mismatches) && shim_env("C4GPU_VERBOSE")){
+                register Optimal *o = ref->span && (i < hp->n_cand) ? ref->span->dst_optimal : ref->optimal;
+                g_message("c4gpu bsdp: check: first mismatch under [%s], region %d %d %d %d%s: reference %d, device %d",
+                          o->name, ref->r[0], ref->r[1], ref->r[2], ref->r[3], ref->span ? " (span src)" : "",
+                          ref->raw, dev ? dev->raw : 0);
+                }
+            st.mismatches++;
+            }
+        g_free(ref->ops);
+        }
+    /* ... and the other way round: a src traceback the device delivered that the reference never ran */
+    for(k = hp->n_cand; k < hp->sars->len; k++){
+        register gboolean found = FALSE;
+        for(i = hp->n_cand; (!found) && (i < chk.sars->len); i++)
+            found = sar_equal(&g_array_index(hp->sars, ShimSar, k), &g_array_index(chk.sars, ShimSar, i));
+        if(!found){
+            st.checked++;
+            st.mismatches++;
+            }
+        }
+    g_array_free(chk.sars, TRUE);
+    return;
+    }
+static gboolean bsdp_check_on(void){
+    register const gchar *e = shim_env("C4GPU_BSDP_CHECK");
+    return e && (atoi(e) == 1);
     }
 
 /* what Heuristic_Span_dst_init_start_func (heuristic.c:414-443) returns for every cell of the dst region, as the
@@ -477,7 +552,7 @@ static gboolean bsdp_device_scores(GPtrArray *todo, c4gpu_batch **batch_out){
         }
     hp = todo->pdata[0];
     ud = Model_Type_create_data(gam->gas->type, hp->comparison->query, hp->comparison->target);
-    if(shim_flatten_any(gam->heuristic->model, ud, &fm, FALSE)){
+    if(bsdp_flatten(gam->heuristic->model, ud, &fm, FALSE)){
         memset(&params, 0, sizeof(params));
         shim_params(ud, &params);
         batch = c4gpu_batch_create(ctx, &fm, &params, pair, n);
@@ -760,7 +835,7 @@ void shim_bsdp_flush(void){
     register GPtrArray *todo = bsdp_pending;
     register gboolean have_scores;
     c4gpu_batch *batch = NULL;
-    gint64 t0 = g_get_monotonic_time(), t1, t2, t3;
+    gint64 t0 = g_get_monotonic_time(), t1, t2, t3, tchk = 0;
     if((!todo) || (!todo->len))
         return;
     bsdp_pending = NULL;
@@ -774,6 +849,7 @@ void shim_bsdp_flush(void){
         if(none)                                   /* cannot happen: no node reaches the dry threshold */
             GAM_Result_destroy(none);
         st.candidates += bsdp_cur->sars->len;
+        bsdp_cur->n_cand = bsdp_cur->sars->len;
         }
     bsdp_cur = NULL;
     bsdp_mode = BSDP_OFF;
@@ -789,6 +865,13 @@ void shim_bsdp_flush(void){
             g_warning("c4gpu: %s -- BSDP sub-DPs stay on the CPU for this batch", c4gpu_last_error());
         }
     t2 = g_get_monotonic_time();
+    if(have_scores && (!shim_env("C4GPU_BSDP_HOST")) && bsdp_check_on()){     /* its time is its own, not the device's */
+        for(i = 0; i < todo->len; i++)
+            bsdp_check(todo->pdata[i]);
+        tchk = g_get_monotonic_time() - t2;
+        st.check_ms += tchk / 1e3;
+        t2 += tchk;
+        }
     for(i = 0; have_scores && (i < todo->len); i++){
         register ShimHPending *hp = todo->pdata[i];
         hp->index = g_hash_table_new(sar_hash, sar_equal);
@@ -832,7 +915,7 @@ void shim_bsdp_flush(void){
         st.pairs++;
         }
     g_ptr_array_free(todo, TRUE);
-    st.dry_ms += (t1 - t0) / 1e3; st.device_ms += (t2 - t1) / 1e3; st.refine_ms += (t3 - t2) / 1e3;
+    st.dry_ms += (t1 - t0) / 1e3; st.device_ms += (t2 - t1 - tchk) / 1e3; st.refine_ms += (t3 - t2) / 1e3;
     st.replay_ms += (g_get_monotonic_time() - t3) / 1e3;
     return;
     }
@@ -840,12 +923,14 @@ void shim_bsdp_flush(void){
 /* A model whose match advances the query by more than one row (both sequences translated: coding2coding, ungapped:trans)
  * is collected exactly when every model BSDP derives from it -- the terminals of every match and the join of every pair of
  * matches -- has a compiled device family: coding2coding's have (FAM_CODING2CODING_START / _END / _JOIN, three query rows per
- * lane), ungapped:trans's have not and keep the reference's route call for call.  An annotated sequence declines as everywhere
+ * lane), ungapped:trans's have not and keep the reference's route call for call.  coding2genome's pairs of matches have spans:
+ * those count only under its own switch (C4GPU_CODING2GENOME_BSDP=1), and then each span's src, dst and src traceback model must
+ * have a family as well (FAM_CODING2GENOME_PHASE{0,1,2}_SPAN_SRC / _DST).  An annotated sequence declines as everywhere
  * (shim_flatten_any: the codon match's annotation veto depends on the frame).  Asked once per Heuristic. */
 static gboolean bsdp_wide_model_served(GAM *gam, Comparison *comparison){
     static GHashTable *known = NULL;               /* Heuristic* -> 1 (no) or 2 (yes) */
     register Heuristic *h = gam->heuristic;
-    register gint i, j, answer;
+    register gint i, j, k, o, answer;
     register gboolean ok = TRUE;
     register gpointer ud;
     c4gpu_model fm;
@@ -862,19 +947,36 @@ static gboolean bsdp_wide_model_served(GAM *gam, Comparison *comparison){
         dm[0] = m->start_terminal ? m->start_terminal->terminal_model : NULL;
         dm[1] = m->end_terminal ? m->end_terminal->terminal_model : NULL;
         for(j = 0; ok && (j < 2); j++)
-            if(dm[j] && ((!shim_flatten_any(dm[j]->derived, ud, &fm, TRUE)) || (c4gpu_model_device_family(&fm) < 0)))
+            if(dm[j] && ((!bsdp_flatten(dm[j]->derived, ud, &fm, TRUE)) || (c4gpu_model_device_family(&fm) < 0)))
                 ok = FALSE;
         for(j = 0; ok && (j < h->match_total); j++){
             register Heuristic_Pair *p = h->pair_matrix[i][j];
             if(!p)
                 continue;
-            if((p->span_list && p->span_list->len)
-            || (p->join && ((!shim_flatten_any(p->join->join_model->derived, ud, &fm, TRUE))
-                         || (c4gpu_model_device_family(&fm) < 0))))
+            if(p->join && ((!bsdp_flatten(p->join->join_model->derived, ud, &fm, TRUE))
+                        || (c4gpu_model_device_family(&fm) < 0)))
                 ok = FALSE;
+            if(p->span_list && p->span_list->len){
+                /* spans: only under coding2genome's switch, and then every span's src, dst and src traceback model */
+                if(!bsdp_coding2genome_on())
+                    ok = FALSE;
+                for(k = 0; ok && (k < (gint)p->span_list->len); k++){
+                    register Heuristic_Span *hs = p->span_list->pdata[k];
+                    Optimal *so[3];
+                    so[0] = hs->src_optimal; so[1] = hs->dst_optimal; so[2] = hs->src_traceback_optimal;
+                    for(o = 0; ok && (o < 3); o++){
+                        register C4_Model *sm = so[o]->find_score ? so[o]->find_score->model : so[o]->find_path->model;
+                        if((!bsdp_flatten(sm, ud, &fm, TRUE)) || (c4gpu_model_device_family(&fm) < 0))
+                            ok = FALSE;
+                        }
+                    }
+                }
             }
         }
     Model_Type_destroy_data(gam->gas->type, ud);
+    if((!ok) && shim_env("C4GPU_VERBOSE") && h->model->span_list && h->model->span_list->len)
+        g_message("c4gpu bsdp: model [%s] stays with the reference (a wide-advance model with spans: "
+                  "C4GPU_CODING2GENOME_BSDP=1 serves coding2genome's)", h->model->name);
     g_hash_table_insert(known, h, GINT_TO_POINTER(ok ? 2 : 1));
     return ok;
     }
@@ -917,6 +1019,8 @@ GAM_Result *GAM_Result_heuristic_create(GAM *gam, Comparison *comparison){
     }
 
 void shim_bsdp_report(void){
+    if(st.checked)
+        g_message("c4gpu bsdp: check %ld candidates, %ld mismatches (%.0f ms)", st.checked, st.mismatches, st.check_ms);
     if(shim_env("C4GPU_VERBOSE") && st.pairs)
         g_message("c4gpu bsdp: %ld pairs in %ld flush(es): %ld candidate sub-DPs (%ld spans) in device batches; "
                   "%ld of %ld score calls and %ld of %ld path calls served from them; %ld of %ld refinements from "

@@ -420,12 +420,16 @@ gboolean shim_model_has_query_span(C4_Model *m){
     return FALSE;
     }
 
-gboolean shim_flatten_split_codon(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out){
+gboolean shim_flatten_split_codon_any(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out, gboolean allow_span){
     register gboolean ok;
     shim_split_codon_ok = TRUE;
-    ok = shim_flatten_any(m, ud, out, FALSE);
+    ok = shim_flatten_any(m, ud, out, allow_span);
     shim_split_codon_ok = FALSE;
     return ok;
+    }
+
+gboolean shim_flatten_split_codon(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out){
+    return shim_flatten_split_codon_any(m, ud, out, FALSE);
     }
 
 static gboolean shim_flatten(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out){

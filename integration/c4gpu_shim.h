@@ -22,6 +22,8 @@ gboolean shim_flatten_any(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out, gboo
 /* ... for a seam that serves split codons against a translated DNA query (coding2genome) under a switch of its own, whatever
  * C4GPU_CODING2GENOME (the exhaustive seam's switch) says */
 gboolean shim_flatten_split_codon(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out);
+/* ... and with BSDP's span models allowed (the BSDP seam, C4GPU_CODING2GENOME_BSDP=1) */
+gboolean shim_flatten_split_codon_any(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out, gboolean allow_span);
 /* TRUE when some span of the model (C4_Model_add_span) loops on the query axis: the device SDP passes and BSDP's compiled span
  * families only know spans along the target (introns), so the heuristic seams leave such a model (ner: a span on both axes,
  * ner.c:105) to the reference's own functions */

@@ -23,8 +23,14 @@ DERIVED_VARIANTS = [("MODE_SCORE", 0, 0, 0), ("MODE_PATH", 0, 0, 0)]
 # on one strip and runs T + 64 steps whatever the lanes hold, so a fourth row would be a third more work per step
 # for nothing (a strip of 192 rows covers the rectangles BSDP's ranges ask for), and at four rows the score kernels spill too
 # (profiles/codon_heuristic.md)
-DERIVED_R = {"coding2coding": 3}
+DERIVED_R = {"coding2coding": 3, "coding2genome": 3}
 DERIVED_FAMILIES += [("FAM_CODING2CODING_%s" % k.upper(), "Coding2Coding%sDesc" % k, "coding2coding_%s" % k.lower())
+                     for k in ("Start", "End", "Join")]
+# coding2genome's: 14 states with the shadow and its base slot at three rows per lane, one wave per SIMD (profiles/coding2genome_heuristic.md)
+# ... and held to one wave per SIMD, not the four of the other derived kernels: under the 128-register cap its span src score
+# kernel keeps 1.2 KB per lane in scratch
+DERIVED_CAP = {"coding2genome": 1}
+DERIVED_FAMILIES += [("FAM_CODING2GENOME_%s" % k.upper(), "Coding2Genome%sDesc" % k, "coding2genome_%s" % k.lower())
                      for k in ("Start", "End", "Join")]
 # (mode, cont, local, pack)
 VARIANTS = [("MODE_SCORE", 0, 1, 0), ("MODE_SCORE", 0, 0, 0), ("MODE_REGION", 0, 1, 1), ("MODE_REGION", 0, 1, 0),
@@ -112,15 +118,18 @@ for fam, desc, short in DERIVED_FAMILIES:
         sym = "k_%s_%s" % (short, mode[5:].lower())
         with open(os.path.join(OUT, sym + ".hip"), "w") as fh:
             fh.write('// generated by tools/gen_kernel_tus.py\n#include "../c4_launch.h"\nnamespace c4k {\n'
-                     'C4K_DEFINE_KERNEL(%s, %s, %d, %s, false, false, false, 4, false)\n}\n'
-                     % (sym, desc, DERIVED_R.get(short.rsplit("_", 1)[0], 1), mode))
+                     'C4K_DEFINE_KERNEL(%s, %s, %d, %s, false, false, false, %d, false)\n}\n'
+                     % (sym, desc, DERIVED_R.get(short.rsplit("_", 1)[0], 1), mode, DERIVED_CAP.get(short.rsplit("_", 1)[0], 4)))
         entries.append((fam, mode, cont, local, pack, 0, sym, 0))
 # est2genome's span models: src (END cells out) and dst (START cells in); the src tables also serve the
 # CORNER/CORNER "src traceback" model (heuristic.c:469-472)
 SPAN = []
 for model, stem, which in (("est2genome", "Est2Genome", "Fwd"), ("est2genome", "Est2Genome", "Rev"),
                            ("protein2genome", "Protein2Genome", "Phase0"), ("protein2genome", "Protein2Genome", "Phase1"),
-                           ("protein2genome", "Protein2Genome", "Phase2")):
+                           ("protein2genome", "Protein2Genome", "Phase2"),
+                           # coding2genome's three spans: rows per lane from DERIVED_R, like its terminals and join
+                           ("coding2genome", "Coding2Genome", "Phase0"), ("coding2genome", "Coding2Genome", "Phase1"),
+                           ("coding2genome", "Coding2Genome", "Phase2")):
     for role, kernels in (("Src", (("MODE_SCORE", 2), ("MODE_SCORE", 0), ("MODE_PATH", 0))), ("Dst", (("MODE_SCORE", 1), ("MODE_PATH", 1)))):
         fam = "FAM_%s_%s_SPAN_%s" % (model.upper(), which.upper(), role.upper())
         desc = "%s%sSpan%sDesc" % (stem, which, role)
@@ -128,7 +137,8 @@ for model, stem, which in (("est2genome", "Est2Genome", "Fwd"), ("est2genome", "
             sym = "k_%s_%s_span_%s_%s%s" % (model, which.lower(), role.lower(), mode[5:].lower(), ("_span%d" % span) if span else "")
             with open(os.path.join(OUT, sym + ".hip"), "w") as fh:
                 fh.write('// generated by tools/gen_kernel_tus.py\n#include "../c4_launch.h"\nnamespace c4k {\n'
-                         'C4K_DEFINE_KERNEL_SPAN(%s, %s, 1, %s, false, false, false, 4, false, %d)\n}\n' % (sym, desc, mode, span))
+                         'C4K_DEFINE_KERNEL_SPAN(%s, %s, %d, %s, false, false, false, %d, false, %d)\n}\n'
+                         % (sym, desc, DERIVED_R.get(model, 1), mode, DERIVED_CAP.get(model, 4), span))
             SPAN.append((fam, mode, span, sym))
 for fam, desc, short in FAMILIES:
     for mode, cont, local, pack in VARIANTS:
