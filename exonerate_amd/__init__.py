@@ -278,6 +278,54 @@ def _wordtab(ctx, width, wordlen, words):
     return tab
 
 
+class WordTable:
+    """A word table built on the device (Engine.wordtab_build, c4gpu_wordtab_build).  seed_scan and seed_extend take it in
+    place of `words` / `emits`.  stats: occurrences, seeded words, neighbour links, words, emissions, build_ms."""
+
+    def __init__(self, ctx, width, wordlen, tab, stats):
+        self.ctx, self.width, self.wordlen, self.tab, self.stats = ctx, width, wordlen, tab, stats
+
+    def export(self):
+        """(codes, emit_first, emits): the words by code ascending, word k's emissions emits[emit_first[k]:emit_first[k + 1]]
+        as (pair, query position); a scan's emission index points into emits (c4gpu_wordtab_export)."""
+        return _wordtab_export(self.ctx, self.tab)
+
+    def close(self):
+        if self.tab:
+            _lib().c4gpu_wordtab_destroy(self.tab)
+            self.tab = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _wordtab_export(ctx, tab):
+    import numpy as np
+    nw, ne = C.c_int64(0), C.c_int64(0)
+    cap_w = cap_e = 0
+    while True:
+        codes = np.zeros(max(1, cap_w), dtype=np.uint64)
+        first = np.zeros(cap_w + 1, dtype=np.int32)
+        emits = np.zeros((max(1, cap_e), 2), dtype=np.int32)
+        if _lib().c4gpu_wordtab_export(ctx, tab, codes.ctypes.data, first.ctypes.data, cap_w, emits.ctypes.data, cap_e,
+                                       C.byref(nw), C.byref(ne)) != 0:
+            raise _err("c4gpu_wordtab_export")
+        if nw.value <= cap_w and ne.value <= cap_e:
+            break
+        cap_w, cap_e = nw.value, ne.value
+    return ([int(c) for c in codes[:nw.value]], [int(f) for f in first[:nw.value + 1]],
+            [(int(p), int(q)) for p, q in emits[:ne.value]])
+
+
 def _viterbi_jobs(jobs):
     cj = (_abi.ViterbiJob * max(1, len(jobs)))()
     for i, j in enumerate(jobs):
@@ -502,12 +550,38 @@ class Engine:
             res.append(mine)
         return res
 
+    def wordtab_build(self, width, wordlen, strings, sources, scores=None, threshold=0, use_dropoff=True):
+        """The seeder's word table built on the device from the queries themselves (c4gpu_wordtab_build: Seeder_insert_query
+        seeder.c:478-558 with the word neighbourhoods of wordhood.c).  strings: the queries as bytes of automaton columns
+        (0 resets), inserted in order; sources: per string (pair, pos_scale, pos_offset) -- a word at pos seeds (pair, pos *
+        pos_scale + pos_offset); scores: width rows of width column scores, or None for no neighbourhoods; threshold /
+        use_dropoff: the word limit and --useworddropoff.  Returns a WordTable."""
+        strs = [bytes(x) for x in strings]
+        if len(sources) != len(strs):
+            raise ValueError("one source per string")
+        sp = (C.c_char_p * max(1, len(strs)))(*strs)
+        sn = (C.c_int32 * max(1, len(strs)))(*[len(x) for x in strs])
+        src = (_abi.WordSource * max(1, len(strs)))(*[_abi.WordSource(*x) for x in sources])
+        sc = None
+        if scores is not None:
+            flat = [int(v) for row in scores for v in row]
+            if len(flat) != width * width:
+                raise ValueError("scores: width rows of width entries")
+            sc = (C.c_int32 * len(flat))(*flat)
+        stats = _abi.WordtabBuildStats()
+        tab = _lib().c4gpu_wordtab_build(self.ctx, width, wordlen, sp, sn, src, len(strs), sc, threshold, int(bool(use_dropoff)),
+                                         C.byref(stats))
+        if not tab:
+            raise _err("c4gpu_wordtab_build")
+        return WordTable(self.ctx, width, wordlen, tab, {k: getattr(stats, k) for k, _ in _abi.WordtabBuildStats._fields_})
+
     def seed_scan(self, width, wordlen, words, symbols):
         """The seeder's word scan on the device (c4gpu_seed_scan).  words: {code: number of emissions} in emission-list
-        order (the k-th word's emissions follow those of the words before it); symbols: bytes of automaton columns
-        (0 = outside the alphabet).  Returns ([(position of the word's last symbol, emission index)], device ms)."""
+        order (the k-th word's emissions follow those of the words before it), or a WordTable; symbols: bytes of automaton
+        columns (0 = outside the alphabet).  Returns ([(position of the word's last symbol, emission index)], device ms)."""
         import numpy as np
-        tab = _wordtab(self.ctx, width, wordlen, words)
+        own = not isinstance(words, WordTable)
+        tab = _wordtab(self.ctx, width, wordlen, words) if own else words.tab
         try:
             n_hits = C.c_int64(0)
             cap = 1 << 16
@@ -522,13 +596,14 @@ class Engine:
             _lib().c4gpu_wordtab_stats(tab, C.byref(ms), None, None, None)
             return [tuple(int(x) for x in r) for r in buf[:n_hits.value]], ms.value
         finally:
-            _lib().c4gpu_wordtab_destroy(tab)
+            if own:
+                _lib().c4gpu_wordtab_destroy(tab)
 
     def seed_extend(self, params, match, pairs, width, wordlen, words, emits, strings, tpos_scale, tpos_offset, tpos_modifier,
                     seedlen, dropoff, threshold, cap=None, first_hits=None, mask_query=False, mask_target=False, seed_repeat=1):
         """Word scan to stored HSPs in one device call (c4gpu_seed_extend): what a fresh HSPset per pair holds after the
         seeder has walked `strings` (the target's symbol strings, walked in order).  words as for seed_scan; emits: the
-        (pair, query position) of every emission.  Returns ([(walk index of the word hit, pair, [query_start, target_start,
+        (pair, query position) of every emission (a WordTable brings its own: emits is not read).  Returns ([(walk index of the word hit, pair, [query_start, target_start,
         length, score, cobs])] in walk order, {"n_hits", "n_extended", "n_below", "n_kept"}).  cap: room for that many
         HSPs and one call only (more kept: an empty list, n_kept says how many); None: call again until they fit.
         first_hits: a list that receives, per pair, the walk index of its first word hit or -1 (c4gpu_seed_extend_first_hits).
@@ -537,9 +612,10 @@ class Engine:
         default the call is c4gpu_seed_extend_opt (hspset.c:950-970,981-995), with the defaults c4gpu_seed_extend."""
         arr, keep = _pairs(pairs)
         kind = match if isinstance(match, int) else _match_kind(match)
-        tab = _wordtab(self.ctx, width, wordlen, words)
+        own = not isinstance(words, WordTable)
+        tab = _wordtab(self.ctx, width, wordlen, words) if own else words.tab
         try:
-            if emits is not None:
+            if own and emits is not None:
                 ce = (_abi.SeedEmit * max(1, len(emits)))(*[_abi.SeedEmit(p, q) for p, q in emits])
                 if _lib().c4gpu_wordtab_set_emissions(tab, ce, len(emits)) != 0:
                     raise _err("c4gpu_wordtab_set_emissions")
@@ -573,7 +649,8 @@ class Engine:
             return ([(out[i].seed, out[i].pair, out[i].hsp.aslist()) for i in range(n)],
                     dict(n_hits=stats.n_hits, n_extended=stats.n_extended, n_below=stats.n_below, n_kept=stats.n_kept))
         finally:
-            _lib().c4gpu_wordtab_destroy(tab)
+            if own:
+                _lib().c4gpu_wordtab_destroy(tab)
 
     @staticmethod
     def sdp_stats(reset=False):

@@ -137,6 +137,15 @@ class SeedExtendStats(C.Structure):
     _fields_ = [("n_hits", C.c_int64), ("n_extended", C.c_int64), ("n_below", C.c_int64), ("n_kept", C.c_int64)]
 
 
+class WordSource(C.Structure):
+    _fields_ = [("pair", C.c_int32), ("pos_scale", C.c_int32), ("pos_offset", C.c_int32)]
+
+
+class WordtabBuildStats(C.Structure):
+    _fields_ = [("n_occurrences", C.c_int64), ("n_seeded_words", C.c_int64), ("n_links", C.c_int64), ("n_words", C.c_int64),
+                ("n_emits", C.c_int64), ("build_ms", C.c_double)]
+
+
 MATCH_DNA2DNA, MATCH_PROTEIN2PROTEIN, MATCH_PROTEIN2DNA, MATCH_CODON2CODON = 0, 1, 2, 3
 
 
@@ -242,6 +251,11 @@ PROTOTYPES = [
                                         C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                         C.POINTER(SeedHsp), C.c_int64, C.POINTER(SeedExtendStats)]),
     ("c4gpu_seed_extend_first_hits", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),
+    ("c4gpu_wordtab_build", C.c_void_p, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32),
+                                         C.POINTER(WordSource), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32,
+                                         C.POINTER(WordtabBuildStats)]),
+    ("c4gpu_wordtab_export", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("c4gpu_sdp_lattice_cells", C.c_double, [C.POINTER(Hsp), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     ("c4gpu_sdp_batch", C.c_int, [C.c_void_p, C.POINTER(Model), C.POINTER(Params), C.POINTER(Pair), C.c_int32, C.POINTER(Hsp),
                                   C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

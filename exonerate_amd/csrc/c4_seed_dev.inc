@@ -190,7 +190,9 @@ __global__ __launch_bounds__(256) void seed_expand_kernel(int n, const int *__re
 // exclusive scan over the whole array -- seed_blockscan_kernel -- is every (digit, block)'s place), then a stable scatter
 constexpr int SEED_SORT_TILE = 64 * 32;
 
-__global__ __launch_bounds__(64) void seed_sort_hist_kernel(const unsigned *__restrict__ keys, long long n, int shift, int n_blocks,
+// (K: unsigned for the horizon slots; unsigned long long for the word codes of c4_wordtab_build.inc)
+template <class K>
+__global__ __launch_bounds__(64) void seed_sort_hist_kernel(const K *__restrict__ keys, long long n, int shift, int n_blocks,
                                                             unsigned long long *__restrict__ hist) {
     __shared__ unsigned h[256];
     for (int x = threadIdx.x; x < 256; x += 64) h[x] = 0;
@@ -198,15 +200,16 @@ __global__ __launch_bounds__(64) void seed_sort_hist_kernel(const unsigned *__re
     const long long base = (long long)blockIdx.x * SEED_SORT_TILE;
     for (int k = 0; k < 32; k++) {
         const long long i = base + k * 64 + threadIdx.x;
-        if (i < n) atomicAdd(&h[(keys[i] >> shift) & 255u], 1u);
+        if (i < n) atomicAdd(&h[(unsigned)(keys[i] >> shift) & 255u], 1u);
     }
     __syncthreads();
     for (int x = threadIdx.x; x < 256; x += 64) hist[(size_t)x * n_blocks + blockIdx.x] = h[x];
 }
 
-__global__ __launch_bounds__(64) void seed_sort_scatter_kernel(const unsigned *__restrict__ keys, const int *__restrict__ vals, long long n,
+template <class K>
+__global__ __launch_bounds__(64) void seed_sort_scatter_kernel(const K *__restrict__ keys, const int *__restrict__ vals, long long n,
                                                                int shift, int n_blocks, const unsigned long long *__restrict__ hist,
-                                                               unsigned *__restrict__ keys_out, int *__restrict__ vals_out) {
+                                                               K *__restrict__ keys_out, int *__restrict__ vals_out) {
     __shared__ unsigned long long off[256];
     for (int x = threadIdx.x; x < 256; x += 64) off[x] = hist[(size_t)x * n_blocks + blockIdx.x];
     __syncthreads();
@@ -215,8 +218,8 @@ __global__ __launch_bounds__(64) void seed_sort_scatter_kernel(const unsigned *_
     for (int k = 0; k < 32; k++) {                                       // 64 keys at a time, in order: stable
         const long long i = base + k * 64 + threadIdx.x;
         const bool active = i < n;
-        const unsigned key = active ? keys[i] : 0u;
-        const unsigned d = (key >> shift) & 255u;
+        const K key = active ? keys[i] : (K)0;
+        const unsigned d = (unsigned)(key >> shift) & 255u;
         unsigned long long same = __ballot(active);                      // the active lanes that hold this lane's digit
         for (int b = 0; b < 8; b++) {
             const bool bit = (d >> b) & 1u;
@@ -329,6 +332,13 @@ struct c4gpu_wordtab {
     DevBuf<c4gpu_word_hit> d_hits;
     double scan_ms = 0;
     long long scans = 0, symbols = 0, hits = 0;
+    // c4gpu_wordtab_export: the words by code ascending with their first emissions (n_words + 1 entries).  A table built on the
+    // device (c4gpu_wordtab_build) keeps them there, one made by c4gpu_wordtab_create keeps what the caller gave
+    bool built = false;
+    DevBuf<unsigned long long> d_codes;
+    DevBuf<int> d_emit_first;
+    std::vector<uint64_t> h_codes;
+    std::vector<int32_t> h_first;
 };
 
 extern "C" c4gpu_wordtab *c4gpu_wordtab_create(c4gpu_ctx *ctx, int32_t width, int32_t wordlen, const uint64_t *codes,
@@ -342,6 +352,8 @@ extern "C" c4gpu_wordtab *c4gpu_wordtab_create(c4gpu_ctx *ctx, int32_t width, in
         std::unique_ptr<c4gpu_wordtab> t(new c4gpu_wordtab);
         t->ctx = ctx; t->width = width; t->wordlen = wordlen; t->n_words = n_words;
         t->n_emissions = n_words > 0 ? emit_first[n_words] : 0;
+        t->h_codes.assign(codes, codes + n_words);
+        if (n_words > 0) t->h_first.assign(emit_first, emit_first + n_words + 1);
         unsigned size = 16;
         while (size < 2u * (unsigned)std::max(1, n_words)) size <<= 1;
         t->mask = size - 1;
@@ -541,9 +553,9 @@ extern "C" int c4gpu_seed_extend_opt(c4gpu_ctx *ctx, c4gpu_wordtab *t, const c4g
         int passes = 0, cur = 0;
         for (unsigned long long v = (unsigned long long)n_slots; v; v >>= 8) passes++;
         for (int p = 0; p < passes; p++, cur ^= 1) {
-            hipLaunchKernelGGL(seed_sort_hist_kernel, dim3(n_tiles), dim3(64), 0, s, t->d_keys[cur].p, N, 8 * p, n_tiles, t->d_hist.p);
+            hipLaunchKernelGGL(seed_sort_hist_kernel<unsigned>, dim3(n_tiles), dim3(64), 0, s, t->d_keys[cur].p, N, 8 * p, n_tiles, t->d_hist.p);
             hipLaunchKernelGGL(seed_blockscan_kernel, dim3(1), dim3(1024), 0, s, t->d_hist.p, 256 * n_tiles, t->d_report.p + 3);
-            hipLaunchKernelGGL(seed_sort_scatter_kernel, dim3(n_tiles), dim3(64), 0, s, t->d_keys[cur].p, t->d_vals[cur].p, N, 8 * p, n_tiles,
+            hipLaunchKernelGGL(seed_sort_scatter_kernel<unsigned>, dim3(n_tiles), dim3(64), 0, s, t->d_keys[cur].p, t->d_vals[cur].p, N, 8 * p, n_tiles,
                                t->d_hist.p, t->d_keys[cur ^ 1].p, t->d_vals[cur ^ 1].p);
         }
         // the masks of the flagged sides, from the raw residues the batch keeps (the 64 bytes of padding included: hsp_extend_host)
@@ -614,3 +626,5 @@ extern "C" int c4gpu_seed_extend_first_hits(c4gpu_ctx *ctx, c4gpu_wordtab *t, in
     HIP_OK(c4_stream_sync(ctx->stream));                                              // (no hit: ~0 is -1)
     return 0;
 }
+
+#include "c4_wordtab_build.inc"

@@ -20,6 +20,7 @@
  *   c4gpu_seed_scan          <->  Seeder_add_target's automaton walk src/comparison/seeder.c:649-720,852-915
  *   c4gpu_seed_extend        <->  that walk with Seeder_WordInfo_seed and HSPset_seed_hsp behind it  seeder.c:624-647, hspset.c:933-997
  *   c4gpu_seed_extend_opt    <->  the same for soft-masked sets and --seedrepeat  src/comparison/hspset.c:950-970,981-995
+ *   c4gpu_wordtab_build      <->  Seeder_add_query's inserts and word neighbourhoods  src/comparison/seeder.c:478-558, wordhood.c:192-341
  *   c4gpu_sdp_batch          <->  GAM_Result_SDP_create's loop (SDP_Pair_next_path) src/hub/gam.c:852-890, src/sdp/sdp.c:743
  */
 #ifndef INCLUDED_C4GPU_H
@@ -591,6 +592,44 @@ int         c4gpu_seed_extend_opt(c4gpu_ctx *ctx, c4gpu_wordtab *t, const c4gpu_
  * loop of Seeder_add_target (seeder.c:899-913) follows that order: a caller that reports per pair needs it.  n_pairs: that
  * call's.  8 bytes per pair come down. */
 int         c4gpu_seed_extend_first_hits(c4gpu_ctx *ctx, c4gpu_wordtab *t, int64_t *first_hit, int32_t n_pairs);
+
+/* The word table built on the device from the queries themselves: what Seeder_add_query -> Seeder_load_query ->
+ * Seeder_insert_query (src/comparison/seeder.c:478-558,571-614) leaves in the automaton, word neighbourhoods
+ * (src/comparison/wordhood.c) included, with every emission list in the order Seeder_FSM_traverse_func (seeder.c:674-692)
+ * walks it.  `symbols`: n_strings strings of automaton columns as for c4gpu_seed_scan (0 resets: seeder.c:501-514), inserted
+ * in order; string s has the source src[s].
+ *   occurrences   position i of a string ends a word when its last `wordlen` columns are letters (seeder.c:499-519); the word
+ *                 starts at pos = i - wordlen + 1, its seed is (pair, pos * pos_scale + pos_offset) (seeder.c:540-545; a
+ *                 translated frame f: scale 3, offset f - 1).  Numbered g = 0, 1, ... string by string, position ascending.
+ *   own(c)        the seeds of the occurrences of code c, g DESCENDING (seed lists are prepended, seeder.c:103-107)
+ *   hood(W)       walked once, when W gets its first seed (seeder.c:546-553; first(W) = its smallest g).  With T = sum_k
+ *                 s[W_k][W_k] - threshold under use_dropoff, else T = threshold (wordhood.c:331-337): N is in hood(W) iff for
+ *                 EVERY prefix length d = 1 .. wordlen  sum_{k<d} s[W_k][N_k] >= T - sum_{k>=d} s[W_k][W_k]  (the pruned walk,
+ *                 wordhood.c:192-218,277-299: a condition on prefixes, not on the whole word), N != W (seeder.c:470).
+ *                 scores: s[a * width + b] over columns; NULL: no neighbourhoods (HSP_Param_refresh_wordhood, hspset.c:151).
+ *   emissions(N)  own(N), then own(W) for every W with N in hood(W), first(W) DESCENDING (neighbour lists are prepended,
+ *                 seeder.c:121-124).  The table's words are the codes whose list is not empty.
+ * The table comes with its emissions set: c4gpu_seed_scan, c4gpu_seed_extend{,_opt} and c4gpu_seed_extend_first_hits work on
+ * it as on one made by c4gpu_wordtab_create + c4gpu_wordtab_set_emissions, and a scan's `emit` indexes the exported `emits`
+ * (c4gpu_seed_extend then wants every source's pair inside its `pairs`).
+ * Deterministic: two builds of one input give the same table, byte for byte.  Only five counts come back to the host on the
+ * way.  Not served (the caller keeps the reference's automaton for these): --saturatethreshold, --wordjump > 1, annotated
+ * queries (Seeder_word_is_valid, seeder.c:214-240).
+ * Fails (NULL, c4gpu_last_error) before anything is launched: width outside 2 .. 255, wordlen outside 1 .. 32, width^wordlen
+ * beyond 63 bits; a negative length; a source with a negative pair or offset or a scale below 1; more than 2^31 - 1 symbols;
+ * a score beyond +-2^20.  Fails after the counts are known: more than 2^31 - 1 neighbour links or emissions. */
+typedef struct { int32_t pair, pos_scale, pos_offset; } c4gpu_word_source;
+typedef struct { int64_t n_occurrences, n_seeded_words, n_links, n_words, n_emits; double build_ms; } c4gpu_wordtab_build_stats;
+c4gpu_wordtab *c4gpu_wordtab_build(c4gpu_ctx *ctx, int32_t width, int32_t wordlen,
+                                   const uint8_t *const *symbols, const int32_t *n_symbols, const c4gpu_word_source *src,
+                                   int32_t n_strings, const int32_t *scores /* width * width, or NULL */, int32_t threshold,
+                                   int32_t use_dropoff, c4gpu_wordtab_build_stats *stats /* may be NULL */);
+/* A table's words by code ascending: codes[k], its emissions emits[emit_first[k] .. emit_first[k + 1]) -- emit_first has
+ * n_words + 1 entries (room: cap_words + 1).  When *n_words > cap_words or *n_emits > cap_emits nothing else is written and
+ * the call returns 0 (come back with room).  Also for a table made by c4gpu_wordtab_create + _set_emissions whose words were
+ * given by code ascending (otherwise -1: emit_first would not delimit the lists). */
+int         c4gpu_wordtab_export(c4gpu_ctx *ctx, c4gpu_wordtab *t, uint64_t *codes, int32_t *emit_first, int64_t cap_words,
+                                 c4gpu_seed_emit *emits, int64_t cap_emits, int64_t *n_words, int64_t *n_emits);
 
 /* SDP, the default gapped-extension heuristic (SDP_Pair_next_path src/sdp/sdp.c:743 in the loop of GAM_Result_SDP_create
  * src/hub/gam.c:852-890), for every pair of a batch, in the flavour SDP_create picks for the model (sdp.c:322-366):

@@ -14,7 +14,8 @@
  *      walk order and are handed to HSPset_seed_hsp exactly as Seeder_WordInfo_seed does (seeder.c:624-647) — whose
  *      front (c4gpu_hsp.c) batches the extensions on the device;
  *   3. the report loop of Seeder_add_target (seeder.c:899-913) follows unchanged.
- * Building the automaton (Seeder_add_query, word neighbourhoods) stays the reference's.  Not taken (the reference's own
+ * Building the automaton (Seeder_add_query, word neighbourhoods) stays the reference's; with C4GPU_SEED_BUILD=1 (opt-in, below)
+ * step 1 does not read it but builds the table on the device from the queries (c4gpu_wordtab_build).  Not taken (the reference's own
  * function runs): --saturatethreshold (a per-word running count in walk order), --wordambiguity > 1, seeders with both
  * a DNA and a codon loader, a seeder whose automaton was compiled before this front saw it, and -- unless C4GPU_CODON_SEED=1
  * (opt-in) -- a seeder with a translated query (ungapped:trans, coding2coding: the words of the query's three frames in one
@@ -44,6 +45,9 @@
 #include "sequence.h"
 #include "fsm.h"
 #include "vfsm.h"
+#include "submat.h"
+#include "alphabet.h"
+#include "wordhood.h"
 
 #include "c4gpu.h"
 #include "c4gpu_shim.h"
@@ -77,7 +81,8 @@ typedef struct {
 static GHashTable *seed_tabs = NULL;      /* Seeder* -> ShimSeedTab* */
 static GArray *seed_record = NULL;        /* C4GPU_SEED_CHECK: what the reference's own walk hands to HSPset_seed_hsp */
 static struct { long targets, cpu_targets, scans, symbols, hits, checked, words, emits; double scan_ms, host_ms, table_ms;
-                long fused_targets, fused_hits, fused_extended, fused_kept; double fused_ms; } sdst;
+                long fused_targets, fused_hits, fused_extended, fused_kept; double fused_ms;
+                long read, built; double build_ms; } sdst;
 
 gboolean shim_seed_recording(HSPset *hsp_set, guint query_start, guint target_start){
     ShimSeedRec r;
@@ -248,16 +253,200 @@ static ShimSeedTab *seed_state(Seeder *seeder){
     return st;
     }
 
+/* ---- C4GPU_SEED_BUILD=1 (opt-in): step 1 on the device ----
+ * The word table comes from c4gpu_wordtab_build, fed the seeder's own queries, instead of being read off the automaton word by
+ * word.  For a seeder with exactly one loader, no codon loader, no saturate threshold, a word jump of 1 and no annotated query
+ * (Seeder_word_is_valid); any other seeder takes the trie read as before.  The reference's Seeder_add_query has still run -- its
+ * memory accounting (seeder.c:612) decides where a query chunk ends, and its walk stays the fallback -- so this switch does NOT
+ * remove the host automaton: it removes reading it.  C4GPU_SEED_BUILD_CHECK=1 also reads the trie and compares the two tables
+ * word for word and emission for emission. */
+static gboolean seed_build_wanted(ShimSeedTab *st){
+    register Seeder *seeder = st->seeder;
+    register guint k;
+    if((!shim_env("C4GPU_SEED_BUILD")) || (!atoi(shim_env("C4GPU_SEED_BUILD"))) || shim_env("C4GPU_SEED_HOST"))
+        return FALSE;
+    if(seeder->codon_loader || seeder->saturate_threshold || (seeder->sas->word_jump != 1)
+    || ((seeder->dna_loader ? 1 : 0) + (seeder->protein_loader ? 1 : 0) != 1))
+        return FALSE;
+    for(k = 0; k < seeder->query_info_list->len; k++)
+        if(((Seeder_QueryInfo*)seeder->query_info_list->pdata[k])->query->annotation)
+            return FALSE;
+    return TRUE;
+    }
+
+/* st->width / st->column are set.  Fills st->codes / first / emits from the exported table and leaves the table in st->tab */
+static gboolean seed_build_device(ShimSeedTab *st){
+    register Seeder *seeder = st->seeder;
+    register Seeder_Loader *loader = seeder->dna_loader ? seeder->dna_loader : seeder->protein_loader;
+    register HSP_Param *param = loader->hsp_param;
+    register Match *match = param->match;
+    register gboolean translated = match->query->is_translated;
+    register gint n_queries = seeder->query_info_list->len, n_strings = n_queries * (translated ? 3 : 1), i, a, b;
+    register guchar **sym = g_new0(guchar*, n_strings + 1);
+    register gint32 *n_sym = g_new0(gint32, n_strings + 1);
+    register c4gpu_word_source *src = g_new0(c4gpu_word_source, n_strings + 1);
+    register gint32 *scores = NULL;
+    register gboolean ok = TRUE;
+    register guint64 *codes;
+    register c4gpu_seed_emit *emits;
+    register gint32 *first;
+    c4gpu_wordtab_build_stats stats;
+    int64_t n_words = 0, n_emits = 0;
+    guchar insert[ALPHABETSIZE];
+    /* the column a query symbol is inserted under, 0 exactly where seeder.c:501-514 resets */
+    for(i = 0; i < ALPHABETSIZE; i++){
+        if(seeder->seeder_fsm){
+            insert[i] = Alphabet_symbol_is_member(match->comparison_alphabet, i) ? seeder->seeder_fsm->fsm->insertion_filter[i] : 0;
+        } else
+            insert[i] = st->column[i];
+        }
+    insert[0] = 0;
+    for(i = 0; ok && (i < n_strings); i++){
+        register Seeder_QueryInfo *query_info = seeder->query_info_list->pdata[translated ? i / 3 : i];
+        register Sequence *seq = translated ? Sequence_translate(query_info->query, match->mas->translate, (i % 3) + 1)
+                                            : Sequence_share(query_info->query);
+        register Sequence *masked = Sequence_mask(seq);           /* seeder.c:486-487 */
+        register gchar *str = Sequence_get_str(masked);
+        register gint x;
+        n_sym[i] = seq->len;
+        sym[i] = g_new(guchar, n_sym[i] + 1);
+        for(x = 0; x < n_sym[i]; x++){
+            sym[i][x] = insert[(guchar)str[x]];
+            /* (a member the trie has no column for: FSM_add ends the run on such a word, fsm.c:109-111; not met after Seeder_add_query) */
+            if(seeder->seeder_fsm && (!sym[i][x]) && Alphabet_symbol_is_member(match->comparison_alphabet, (guchar)str[x]))
+                ok = FALSE;
+            }
+        src[i].pair = translated ? i / 3 : i;
+        src[i].pos_scale = translated ? 3 : 1;                    /* seeder.c:540-543 */
+        src[i].pos_offset = translated ? i % 3 : 0;
+        g_free(str);
+        Sequence_destroy(masked);
+        Sequence_destroy(seq);
+        }
+    if(ok && param->wordhood){                                    /* hspset.c:146-167: the loader's submat over the alphabet's members */
+        register Submat *submat = (match->type == Match_Type_DNA2DNA) ? match->mas->dna_submat : match->mas->protein_submat;
+        register const guchar *member = match->comparison_alphabet->member;
+        guchar letter[ALPHABETSIZE];
+        memset(letter, 0, sizeof(letter));
+        for(i = 0; member[i]; i++)
+            letter[insert[member[i]]] = member[i];
+        scores = g_new0(gint32, st->width * st->width);
+        for(a = 1; a < st->width; a++)
+            for(b = 1; b < st->width; b++)
+                if(letter[a] && letter[b])
+                    scores[a * st->width + b] = Submat_lookup(submat, letter[a], letter[b]);
+        }
+    if(ok){
+        st->tab = c4gpu_wordtab_build(shim_get_ctx(), st->width, st->wordlen, (const uint8_t *const *)sym, n_sym, src, n_strings, scores,
+                                      param->wordhood ? param->wordhood->threshold : 0,
+                                      param->wordhood ? (param->wordhood->use_dropoff ? 1 : 0) : 1, &stats);
+        if(!st->tab){
+            g_warning("c4gpu: %s -- the word table is read off the automaton", c4gpu_last_error());
+            ok = FALSE;
+            }
+        }
+    for(i = 0; i < n_strings; i++)
+        g_free(sym[i]);
+    g_free(sym); g_free(n_sym); g_free(src); g_free(scores);
+    if(!ok)
+        return FALSE;
+    codes = g_new(guint64, stats.n_words + 1);
+    first = g_new(gint32, stats.n_words + 2);
+    emits = g_new(c4gpu_seed_emit, stats.n_emits + 1);
+    if((c4gpu_wordtab_export(shim_get_ctx(), st->tab, (uint64_t*)codes, first, stats.n_words, emits, stats.n_emits, &n_words, &n_emits) != 0)
+    || (n_words != stats.n_words) || (n_emits != stats.n_emits)){
+        g_warning("c4gpu: %s -- the word table is read off the automaton", c4gpu_last_error());
+        c4gpu_wordtab_destroy(st->tab);
+        st->tab = NULL;
+        ok = FALSE;
+        }
+    if(ok){
+        g_array_set_size(st->codes, 0); g_array_set_size(st->first, 0); g_array_set_size(st->emits, 0);
+        g_array_append_vals(st->codes, codes, n_words);
+        g_array_append_vals(st->first, first, n_words + 1);
+        for(i = 0; i < n_emits; i++){
+            ShimEmit e;
+            e.query_info = seeder->query_info_list->pdata[emits[i].pair]; e.loader = loader; e.query_pos = emits[i].query_pos;
+            g_array_append_val(st->emits, e);
+            }
+        st->fused_sent = TRUE;                                     /* the built table has its emissions: nothing to send again */
+        sdst.built++; sdst.build_ms += stats.build_ms;
+        }
+    g_free(codes); g_free(first); g_free(emits);
+    return ok;
+    }
+
+/* C4GPU_SEED_BUILD_CHECK: `st` holds the table read off the automaton, `b_*` the built one */
+static void seed_build_check(ShimSeedTab *st, GArray *b_codes, GArray *b_first, GArray *b_emits){
+    register guint k, w = 0, n = 0;
+    register glong mismatches = 0;
+    for(k = 0; k < st->codes->len; k++){
+        register gint32 lo = g_array_index(st->first, gint32, k), hi = g_array_index(st->first, gint32, k + 1), e;
+        if(hi == lo)
+            continue;                                              /* a word without emissions is not a word of the table */
+        n++;
+        if((w >= b_codes->len) || (g_array_index(b_codes, guint64, w) != g_array_index(st->codes, guint64, k))
+        || ((g_array_index(b_first, gint32, w + 1) - g_array_index(b_first, gint32, w)) != (hi - lo))){
+            mismatches++;
+            if((w < b_codes->len) && (g_array_index(b_codes, guint64, w) <= g_array_index(st->codes, guint64, k)))
+                w++;
+            continue;
+            }
+        for(e = 0; e < hi - lo; e++){
+            register ShimEmit *x = &g_array_index(st->emits, ShimEmit, lo + e);
+            register ShimEmit *y = &g_array_index(b_emits, ShimEmit, g_array_index(b_first, gint32, w) + e);
+            if((x->query_info != y->query_info) || (x->loader != y->loader) || (x->query_pos != y->query_pos))
+                mismatches++;
+            }
+        w++;
+        }
+    mismatches += b_codes->len - w;
+    g_message("c4gpu seed: build check %u words, %ld mismatches", n, mismatches);
+    return;
+    }
+
 static gboolean seed_build(ShimSeedTab *st){
     register Seeder *seeder = st->seeder;
     register gint i;
     gint32 zero = 0;
     gint64 t_begin = g_get_monotonic_time();
+    GArray *b_codes = NULL, *b_first = NULL, *b_emits = NULL;
     st->wordlen = seeder->any_hsp_param->wordlen;
     st->codes = g_array_new(FALSE, FALSE, sizeof(guint64));
     st->first = g_array_new(FALSE, FALSE, sizeof(gint32));
     st->emits = g_array_new(FALSE, FALSE, sizeof(ShimEmit));
+    if(seed_build_wanted(st) && ((!seeder->seeder_vfsm) || ((gint)seeder->seeder_vfsm->vfsm->depth == st->wordlen))){
+        if(seeder->seeder_fsm){
+            st->width = seeder->seeder_fsm->fsm->width;
+            for(i = 0; i < ALPHABETSIZE; i++)
+                st->column[i] = seeder->seeder_fsm->fsm->traversal_filter[i];
+        } else {
+            st->width = seeder->seeder_vfsm->vfsm->alphabet_size + 1;
+            st->upper = TRUE;
+            for(i = 0; i < ALPHABETSIZE; i++)
+                st->column[i] = (guchar)seeder->seeder_vfsm->vfsm->index[toupper(i)];
+            }
+        st->column[0] = 0;
+        if(seed_build_device(st)){
+            shim_mark("  word table built on the device");
+            if(!seeder->seeder_fsm)
+                seeder->is_prepared = TRUE;
+            if(!shim_env("C4GPU_SEED_BUILD_CHECK")){
+                st->usable = TRUE;
+                sdst.words += st->codes->len; sdst.emits += st->emits->len;
+                sdst.table_ms += (g_get_monotonic_time() - t_begin) / 1e3;
+                return TRUE;
+                }
+            /* the check: what follows reads the automaton as ever, into arrays of its own */
+            b_codes = st->codes; b_first = st->first; b_emits = st->emits;
+            st->codes = g_array_new(FALSE, FALSE, sizeof(guint64));
+            st->first = g_array_new(FALSE, FALSE, sizeof(gint32));
+            st->emits = g_array_new(FALSE, FALSE, sizeof(ShimEmit));
+            }
+        }
+    g_array_set_size(st->codes, 0); g_array_set_size(st->first, 0); g_array_set_size(st->emits, 0);
     g_array_append_val(st->first, zero);
+    sdst.read++;
     if(seeder->seeder_fsm){
         register FSM *f = seeder->seeder_fsm->fsm;
         st->width = f->width;
@@ -302,7 +491,11 @@ static gboolean seed_build(ShimSeedTab *st){
         }
     if(!seeder->seeder_fsm)
         seeder->is_prepared = TRUE;                            /* (nothing to compile: Seeder_prepare only sets the flag) */
-    if(shim_env("C4GPU_SEED_HOST")){
+    if(b_codes){                                               /* C4GPU_SEED_BUILD_CHECK: compare, then go on with the built table */
+        seed_build_check(st, b_codes, b_first, b_emits);
+        g_array_free(st->codes, TRUE); g_array_free(st->first, TRUE); g_array_free(st->emits, TRUE);
+        st->codes = b_codes; st->first = b_first; st->emits = b_emits;
+    } else if(shim_env("C4GPU_SEED_HOST")){
         st->host_index = g_hash_table_new(g_int64_hash, g_int64_equal);
         for(i = 0; i < (gint)st->codes->len; i++)
             g_hash_table_insert(st->host_index, &g_array_index(st->codes, guint64, i), GINT_TO_POINTER(i + 1));
@@ -869,6 +1062,9 @@ void shim_seed_report(void){
                   "delivery %.0f ms, word tables (%ld words, %ld emissions) %.0f ms%s", sdst.targets, sdst.scans, sdst.symbols,
                   sdst.hits, sdst.scan_ms, sdst.host_ms, sdst.words, sdst.emits, sdst.table_ms,
                   sdst.checked ? "; every seed equal to the reference's own walk" : "");
+    if(shim_env("C4GPU_VERBOSE") && (sdst.read || sdst.built))
+        g_message("c4gpu seed: word tables: %ld read off the automaton, %ld built on the device (c4gpu_wordtab_build %.0f ms)",
+                  sdst.read, sdst.built, sdst.build_ms);
     if(shim_env("C4GPU_VERBOSE") && shim_env("C4GPU_SEED_FUSED") && atoi(shim_env("C4GPU_SEED_FUSED")))
         g_message("c4gpu seed fused: %ld targets through c4gpu_seed_extend: %ld word hits, %ld extensions, %ld HSPs kept "
                   "(%.0f ms with delivery)", sdst.fused_targets, sdst.fused_hits, sdst.fused_extended, sdst.fused_kept, sdst.fused_ms);
