@@ -319,14 +319,11 @@ typedef struct { gint pair, sar; } ShimMember;
 /* C4GPU_CODING2GENOME_BSDP=1: serve coding2genome's heuristic sub-DPs -- its terminals, join and the span src / dst / src
  * traceback models of its three intron phases -- from their device families (off unless asked; C4GPU_CODING2GENOME and
  * C4GPU_CODING2GENOME_SDP are other seams' switches and do not turn this on) */
-static gboolean bsdp_coding2genome_on(void){
-    register const gchar *e = shim_env("C4GPU_CODING2GENOME_BSDP");
-    return e && (atoi(e) == 1);
-    }
-/* the seam's flattening: with that switch the split-codon calcs of a translated DNA query pass */
-static gboolean bsdp_flatten(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out, gboolean allow_span){
-    return bsdp_coding2genome_on() ? shim_flatten_split_codon_any(m, ud, out, allow_span)
-                                   : shim_flatten_any(m, ud, out, allow_span);
+/* the seam's flattening: with that switch, or the exhaustive seam's, the split-codon calcs of a translated DNA query pass
+ * (c4gpu_switches.h); spans: the derived models, whose span cells become matrices -- not the heuristic's whole model */
+static guint bsdp_flatten_flags(gboolean spans){
+    return (spans ? SHIM_FLATTEN_SPANS : 0)
+         | ((shim_is(C4GPU_CODING2GENOME, 1) || shim_is(C4GPU_CODING2GENOME_BSDP, 1)) ? SHIM_FLATTEN_SPLIT_CODON : 0);
     }
 
 static ShimGroup *bsdp_group(GPtrArray *groups, Optimal *optimal, Ungapped_Data *ud){
@@ -339,7 +336,8 @@ static ShimGroup *bsdp_group(GPtrArray *groups, Optimal *optimal, Ungapped_Data 
         }
     g = g_new0(ShimGroup, 1);
     g->optimal = optimal;
-    g->ok = bsdp_flatten(optimal->find_score ? optimal->find_score->model : optimal->find_path->model, ud, &g->fm, TRUE);
+    g->ok = shim_flatten(optimal->find_score ? optimal->find_score->model : optimal->find_path->model, ud, &g->fm,
+                         bsdp_flatten_flags(TRUE));
     g->members = g_array_new(FALSE, FALSE, sizeof(ShimMember));
     g_ptr_array_add(groups, g);
     return g;
@@ -419,21 +417,20 @@ static void bsdp_host_scores(ShimHPending *hp){
         register ShimSar *s = &g_array_index(hp->sars, ShimSar, i);
         Optimal *opts[4];
         register gint o, no = 0;
-        static GHashTable *seen = NULL;
+        static GHashTable *seen = NULL;                /* each Optimal is reported once */
         c4gpu_model fm;
-        if(!seen)
-            seen = g_hash_table_new(g_direct_hash, g_direct_equal);
         if(s->span){ opts[no++] = s->span->src_optimal; opts[no++] = s->span->dst_optimal; opts[no++] = s->span->src_traceback_optimal; }
         else opts[no++] = s->optimal;
         for(o = 0; o < no; o++){
             register C4_Model *m = opts[o]->find_score ? opts[o]->find_score->model : opts[o]->find_path->model;
-            if(g_hash_table_lookup(seen, opts[o]))
+            if(shim_memo_get(&seen, opts[o]))
                 continue;
-            g_hash_table_insert(seen, opts[o], opts[o]);
-            if((!bsdp_flatten(m, ud, &fm, TRUE)) || (c4gpu_model_device_family(&fm) < 0))
+            shim_memo_put(&seen, opts[o], TRUE);
+            register gint family = shim_model_family(m, ud, bsdp_flatten_flags(TRUE), &fm);
+            if(family < 0)
                 g_warning("c4gpu bsdp: model [%s] has no device family", m->name);
-            else if(shim_env("C4GPU_VERBOSE"))
-                g_message("c4gpu bsdp: model [%s] -> device family %d", m->name, c4gpu_model_device_family(&fm));
+            else if(shim_has(C4GPU_VERBOSE))
+                g_message("c4gpu bsdp: model [%s] -> device family %d", m->name, family);
             }
         }
     SubOpt_destroy(empty);
@@ -474,7 +471,7 @@ static void bsdp_check(ShimHPending *hp){
            || (dev->have_path && (!bsdp_same_path(dev, ref)));
         st.checked++;
         if(bad){
-            if((!st.mismatches) && shim_env("C4GPU_VERBOSE")){
+            if((!st.mismatches) && shim_has(C4GPU_VERBOSE)){
                 register Optimal *o = ref->span && (i < hp->n_cand) ? ref->span->dst_optimal : ref->optimal;
                 g_message("c4gpu bsdp: check: first mismatch under [%s], region %d %d %d %d%s: reference %d, device %d",
                           o->name, ref->r[0], ref->r[1], ref->r[2], ref->r[3], ref->span ? " (span src)" : "",
@@ -496,10 +493,6 @@ static void bsdp_check(ShimHPending *hp){
         }
     g_array_free(chk.sars, TRUE);
     return;
-    }
-static gboolean bsdp_check_on(void){
-    register const gchar *e = shim_env("C4GPU_BSDP_CHECK");
-    return e && (atoi(e) == 1);
     }
 
 /* what Heuristic_Span_dst_init_start_func (heuristic.c:414-443) returns for every cell of the dst region, as the
@@ -552,7 +545,7 @@ static gboolean bsdp_device_scores(GPtrArray *todo, c4gpu_batch **batch_out){
         }
     hp = todo->pdata[0];
     ud = Model_Type_create_data(gam->gas->type, hp->comparison->query, hp->comparison->target);
-    if(bsdp_flatten(gam->heuristic->model, ud, &fm, FALSE)){
+    if(shim_flatten(gam->heuristic->model, ud, &fm, bsdp_flatten_flags(FALSE))){
         memset(&params, 0, sizeof(params));
         shim_params(ud, &params);
         batch = c4gpu_batch_create(ctx, &fm, &params, pair, n);
@@ -855,7 +848,7 @@ void shim_bsdp_flush(void){
     bsdp_mode = BSDP_OFF;
     t1 = g_get_monotonic_time();
     /* 3. all candidate DPs of all pairs */
-    if(shim_env("C4GPU_BSDP_HOST")){
+    if(shim_has(C4GPU_BSDP_HOST)){
         for(i = 0; i < todo->len; i++)
             bsdp_host_scores(todo->pdata[i]);
         have_scores = TRUE;
@@ -865,7 +858,7 @@ void shim_bsdp_flush(void){
             g_warning("c4gpu: %s -- BSDP sub-DPs stay on the CPU for this batch", c4gpu_last_error());
         }
     t2 = g_get_monotonic_time();
-    if(have_scores && (!shim_env("C4GPU_BSDP_HOST")) && bsdp_check_on()){     /* its time is its own, not the device's */
+    if(have_scores && (!shim_has(C4GPU_BSDP_HOST)) && shim_is(C4GPU_BSDP_CHECK, 1)){     /* its time is its own, not the device's */
         for(i = 0; i < todo->len; i++)
             bsdp_check(todo->pdata[i]);
         tchk = g_get_monotonic_time() - t2;
@@ -884,7 +877,7 @@ void shim_bsdp_flush(void){
         }
     /* 3b. --refine: the first refinement of every pair as one more batch on the same resident pairs */
     if(have_scores && (((ShimHPending*)todo->pdata[0])->gam->gas->refinement != GAM_Refinement_NONE)
-    && ((ShimHPending*)todo->pdata[0])->gam->optimal && (!shim_env("C4GPU_REFINE_BATCH_OFF")))
+    && ((ShimHPending*)todo->pdata[0])->gam->optimal && (!shim_has(C4GPU_REFINE_BATCH_OFF)))
         bsdp_refine(todo, batch);
     if(batch)
         c4gpu_batch_destroy(batch);
@@ -926,9 +919,10 @@ void shim_bsdp_flush(void){
  * lane), ungapped:trans's have not and keep the reference's route call for call.  coding2genome's pairs of matches have spans:
  * those count only under its own switch (C4GPU_CODING2GENOME_BSDP=1), and then each span's src, dst and src traceback model must
  * have a family as well (FAM_CODING2GENOME_PHASE{0,1,2}_SPAN_SRC / _DST).  An annotated sequence declines as everywhere
- * (shim_flatten_any: the codon match's annotation veto depends on the frame).  Asked once per Heuristic. */
+ * (shim_flatten: the codon match's annotation veto depends on the frame).  Asked once per Heuristic. */
 static gboolean bsdp_wide_model_served(GAM *gam, Comparison *comparison){
-    static GHashTable *known = NULL;               /* Heuristic* -> 1 (no) or 2 (yes) */
+    static GHashTable *known = NULL;               /* Heuristic* -> no / yes */
+    register guint flags = bsdp_flatten_flags(TRUE);
     register Heuristic *h = gam->heuristic;
     register gint i, j, k, o, answer;
     register gboolean ok = TRUE;
@@ -936,10 +930,8 @@ static gboolean bsdp_wide_model_served(GAM *gam, Comparison *comparison){
     c4gpu_model fm;
     if(comparison->query->annotation || comparison->target->annotation)
         return FALSE;
-    if(!known)
-        known = g_hash_table_new(g_direct_hash, g_direct_equal);
-    if((answer = GPOINTER_TO_INT(g_hash_table_lookup(known, h))))
-        return answer == 2;
+    if((answer = shim_memo_get(&known, h)))
+        return answer == SHIM_MEMO_YES;
     ud = Model_Type_create_data(gam->gas->type, comparison->query, comparison->target);
     for(i = 0; ok && (i < h->match_total); i++){
         register Heuristic_Match *m = h->match_list[i];
@@ -947,18 +939,17 @@ static gboolean bsdp_wide_model_served(GAM *gam, Comparison *comparison){
         dm[0] = m->start_terminal ? m->start_terminal->terminal_model : NULL;
         dm[1] = m->end_terminal ? m->end_terminal->terminal_model : NULL;
         for(j = 0; ok && (j < 2); j++)
-            if(dm[j] && ((!bsdp_flatten(dm[j]->derived, ud, &fm, TRUE)) || (c4gpu_model_device_family(&fm) < 0)))
+            if(dm[j] && (shim_model_family(dm[j]->derived, ud, flags, &fm) < 0))
                 ok = FALSE;
         for(j = 0; ok && (j < h->match_total); j++){
             register Heuristic_Pair *p = h->pair_matrix[i][j];
             if(!p)
                 continue;
-            if(p->join && ((!bsdp_flatten(p->join->join_model->derived, ud, &fm, TRUE))
-                        || (c4gpu_model_device_family(&fm) < 0)))
+            if(p->join && (shim_model_family(p->join->join_model->derived, ud, flags, &fm) < 0))
                 ok = FALSE;
             if(p->span_list && p->span_list->len){
                 /* spans: only under coding2genome's switch, and then every span's src, dst and src traceback model */
-                if(!bsdp_coding2genome_on())
+                if(!shim_is(C4GPU_CODING2GENOME_BSDP, 1))
                     ok = FALSE;
                 for(k = 0; ok && (k < (gint)p->span_list->len); k++){
                     register Heuristic_Span *hs = p->span_list->pdata[k];
@@ -966,7 +957,7 @@ static gboolean bsdp_wide_model_served(GAM *gam, Comparison *comparison){
                     so[0] = hs->src_optimal; so[1] = hs->dst_optimal; so[2] = hs->src_traceback_optimal;
                     for(o = 0; ok && (o < 3); o++){
                         register C4_Model *sm = so[o]->find_score ? so[o]->find_score->model : so[o]->find_path->model;
-                        if((!bsdp_flatten(sm, ud, &fm, TRUE)) || (c4gpu_model_device_family(&fm) < 0))
+                        if(shim_model_family(sm, ud, flags, &fm) < 0)
                             ok = FALSE;
                         }
                     }
@@ -974,11 +965,10 @@ static gboolean bsdp_wide_model_served(GAM *gam, Comparison *comparison){
             }
         }
     Model_Type_destroy_data(gam->gas->type, ud);
-    if((!ok) && shim_env("C4GPU_VERBOSE") && h->model->span_list && h->model->span_list->len)
+    if((!ok) && shim_has(C4GPU_VERBOSE) && h->model->span_list && h->model->span_list->len)
         g_message("c4gpu bsdp: model [%s] stays with the reference (a wide-advance model with spans: "
-                  "C4GPU_CODING2GENOME_BSDP=1 serves coding2genome's)", h->model->name);
-    g_hash_table_insert(known, h, GINT_TO_POINTER(ok ? 2 : 1));
-    return ok;
+                  SHIM_SWITCH_NAME(C4GPU_CODING2GENOME_BSDP) "=1 serves coding2genome's)", h->model->name);
+    return shim_memo_put(&known, h, ok);
     }
 
 GAM_Result *GAM_Result_heuristic_create(GAM *gam, Comparison *comparison){
@@ -987,8 +977,8 @@ GAM_Result *GAM_Result_heuristic_create(GAM *gam, Comparison *comparison){
         && (bsdp_mode == BSDP_OFF)
         && (!shim_model_has_query_span(gam->heuristic->model))   /* no compiled families for a span on both axes (ner) */
         && (!Comparison_Param_get_HSPSet_Argument_Set(comparison->param)->geneseed_threshold)
-        && (shim_env("C4GPU_BSDP_HOST") || (shim_ctx_nowait() != NULL))
-        && (!shim_env("C4GPU_BSDP_OFF"))
+        && (shim_has(C4GPU_BSDP_HOST) || (shim_ctx_nowait() != NULL))
+        && (!shim_has(C4GPU_BSDP_OFF))
         /* a query advance of 3: only where the derived models have device families (coding2coding; not ungapped:trans) */
         && ((!shim_model_has_wide_query_advance(gam->heuristic->model)) || bsdp_wide_model_served(gam, comparison));
     /* --gappedextension yes: the SDP seam (c4gpu_sdp.c) takes the pairs of the models it covers */
@@ -1021,7 +1011,7 @@ GAM_Result *GAM_Result_heuristic_create(GAM *gam, Comparison *comparison){
 void shim_bsdp_report(void){
     if(st.checked)
         g_message("c4gpu bsdp: check %ld candidates, %ld mismatches (%.0f ms)", st.checked, st.mismatches, st.check_ms);
-    if(shim_env("C4GPU_VERBOSE") && st.pairs)
+    if(shim_has(C4GPU_VERBOSE) && st.pairs)
         g_message("c4gpu bsdp: %ld pairs in %ld flush(es): %ld candidate sub-DPs (%ld spans) in device batches; "
                   "%ld of %ld score calls and %ld of %ld path calls served from them; %ld of %ld refinements from "
                   "refinement batches; dry runs %.0f ms, device %.0f ms, refinement %.0f ms, replay %.0f ms", st.pairs,

@@ -40,24 +40,21 @@ static GHashTable *hsp_pending = NULL;          /* HSPset* -> ShimSeedSet* */
 static GPtrArray *hsp_order = NULL;             /* ShimSeedSet*, in order of first seed */
 static struct { long sets, seeds, stored, dropped, checked, flushes; double device_ms; } hst;
 
-/* C4GPU_CODON_SEED=1 (opt-in): the seeds of the translated models (ungapped:trans, coding2coding) are taken too */
-gboolean shim_codon_seed(void){
-    static gint on = -1;
-    if(on < 0)
-        on = (shim_env("C4GPU_CODON_SEED") && atoi(shim_env("C4GPU_CODON_SEED"))) ? 1 : 0;
-    return on;
-    }
-
-static gint hsp_match_kind(HSPset *hsp_set){
-    switch(hsp_set->param->match->type){
+gint shim_match_kind(Match_Type type, gboolean annotated_query){
+    switch(type){
         case Match_Type_DNA2DNA: return C4GPU_MATCH_DNA2DNA;
         case Match_Type_PROTEIN2PROTEIN: return C4GPU_MATCH_PROTEIN2PROTEIN;
         case Match_Type_PROTEIN2DNA: return C4GPU_MATCH_PROTEIN2DNA;
-        /* behind the switch; a query with an annotation keeps the reference's function, which vetoes codons outside the CDS
-         * frame inside the score (Match_3_3_split_score_func, match.c:513-519) */
-        case Match_Type_CODON2CODON: return (shim_codon_seed() && !hsp_set->query->annotation) ? C4GPU_MATCH_CODON2CODON : -1;
+        /* C4GPU_CODON_SEED (opt-in): the seeds of the translated models (ungapped:trans, coding2coding) are taken too; a query
+         * with an annotation keeps the reference's function, which vetoes codons outside the CDS frame inside the score
+         * (Match_3_3_split_score_func, match.c:513-519) */
+        case Match_Type_CODON2CODON: return (shim_nonzero(C4GPU_CODON_SEED) && !annotated_query) ? C4GPU_MATCH_CODON2CODON : -1;
         default: return -1;
         }
+    }
+
+static gint hsp_match_kind(HSPset *hsp_set){
+    return shim_match_kind(hsp_set->param->match->type, hsp_set->query->annotation != NULL);
     }
 
 static const gchar *hsp_match_name(HSPset *hsp_set){
@@ -78,10 +75,7 @@ static gint hsp_section(HSPset *hsp_set, guint query_start, guint target_start){
     }
 
 static gboolean hsp_eligible(HSPset *hsp_set){
-    static gint off = -1;
-    if(off < 0)
-        off = shim_env("C4GPU_HSP_OFF") ? 1 : 0;
-    if(off || (!hsp_set->horizon) || (hsp_set->param->seed_repeat > 1) || (hsp_match_kind(hsp_set) < 0))
+    if(shim_has(C4GPU_HSP_OFF) || (!hsp_set->horizon) || (hsp_set->param->seed_repeat > 1) || (hsp_match_kind(hsp_set) < 0))
         return FALSE;
     if(shim_batch_size() <= 0)
         return FALSE;
@@ -89,7 +83,7 @@ static gboolean hsp_eligible(HSPset *hsp_set){
      * being opened, shim_ctx_nowait) stays with that function: the replay starts from an empty set */
     if(!hsp_set->is_empty)
         return FALSE;
-    return shim_env("C4GPU_HSP_HOST") || (shim_ctx_nowait() != NULL);
+    return shim_has(C4GPU_HSP_HOST) || (shim_ctx_nowait() != NULL);
     }
 
 void HSPset_seed_hsp(HSPset *hsp_set, guint query_start, guint target_start){
@@ -184,7 +178,7 @@ static void hsp_check(ShimSeedSet *ss, const c4gpu_hsp *hsp, const gint32 *dropp
             same = (ref.query_start == hsp[k].query_start) && (ref.target_start == hsp[k].target_start)
                 && (ref.length == hsp[k].length) && (ref.score == hsp[k].score);
         if(!same)
-            g_error("C4GPU_HSP_CHECK: seed (%u, %u) of [%s] vs [%s]: device %s (%d, %d, %d, score %d), reference %s (%d, %d, %d, score %d)",
+            g_error(SHIM_SWITCH_NAME(C4GPU_HSP_CHECK) ": seed (%u, %u) of [%s] vs [%s]: device %s (%d, %d, %d, score %d), reference %s (%d, %d, %d, score %d)",
                     seed[0], seed[1], hsp_set->query->id, hsp_set->target->id,
                     dropped[k] ? "dropped" : "kept", hsp[k].query_start, hsp[k].target_start, hsp[k].length, hsp[k].score,
                     ref_dropped ? "dropped, masked end" : "kept", ref.query_start, ref.target_start, ref.length, ref.score);
@@ -242,8 +236,8 @@ static void hsp_dump_set(ShimSeedSet *ss, const gchar *qstr, const gchar *tstr){
     static FILE *fp = NULL;
     register HSPset *set = ss->set;
     register guint k;
-    if(!fp && !(fp = fopen(shim_env("C4GPU_HSP_DUMP"), "a")))
-        g_error("C4GPU_HSP_DUMP: cannot open [%s]", shim_env("C4GPU_HSP_DUMP"));
+    if(!fp && !(fp = fopen(shim_text(C4GPU_HSP_DUMP), "a")))
+        g_error(SHIM_SWITCH_NAME(C4GPU_HSP_DUMP) ": cannot open [%s]", shim_text(C4GPU_HSP_DUMP));
     fprintf(fp, "{\"query_id\":");
     hsp_dump_str(fp, set->query->id);
     fprintf(fp, ",\"target_id\":");
@@ -328,7 +322,7 @@ static void hsp_flush(void){
      * device a chain's seeds are taken in order and the ones below the running horizon are not extended at all
      * (c4gpu_hsp_extend_chains): a long identical diagonal costs one extension instead of one per word hit.
      * C4GPU_HSP_CHAIN=0: every seed is extended and the replay alone applies the horizon */
-    if(!shim_env("C4GPU_HSP_HOST") && !(shim_env("C4GPU_HSP_CHAIN") && !atoi(shim_env("C4GPU_HSP_CHAIN")))){
+    if(!shim_has(C4GPU_HSP_HOST) && !shim_is(C4GPU_HSP_CHAIN, 0)){
         register GArray *h0 = g_array_new(FALSE, FALSE, sizeof(gint32));
         chain_of = g_new(gint32, total + 1);
         for(i = 0; i < n_sets; i++){
@@ -365,7 +359,7 @@ static void hsp_flush(void){
         n_chains = h0->len;
         horizon0 = (gint32*)g_array_free(h0, FALSE);
         }
-    if(shim_env("C4GPU_HSP_HOST")){
+    if(shim_has(C4GPU_HSP_HOST)){
         /* the reference's own extension, one scratch HSPset per seed (hsp_host_one) */
         for(i = 0; i < n_sets; i++){
             register ShimSeedSet *ss = hsp_order->pdata[i];
@@ -435,7 +429,7 @@ static void hsp_flush(void){
             }
 #undef HSP_SAME_GROUP
         g_free(done);
-        if(ok && shim_env("C4GPU_HSP_CHECK"))
+        if(ok && shim_has(C4GPU_HSP_CHECK))
             for(i = 0; i < n_sets; i++)
                 hsp_check(hsp_order->pdata[i], hsps + set_first[i], dropped + set_first[i]);
         }
@@ -448,7 +442,7 @@ static void hsp_flush(void){
             for(k = 0; k < ss->seeds->len; k++)
                 HSPset_seed_hsp_cpu(ss->set, g_array_index(ss->seeds, guint, 2 * k), g_array_index(ss->seeds, guint, 2 * k + 1));
             }
-        if(shim_env("C4GPU_HSP_DUMP"))
+        if(shim_has(C4GPU_HSP_DUMP))
             hsp_dump_set(ss, g_hash_table_lookup(seq_index, ss->set->query), g_hash_table_lookup(seq_index, ss->set->target));
         hst.sets++; hst.seeds += ss->seeds->len;
         g_array_free(ss->seeds, TRUE);
@@ -475,7 +469,7 @@ HSPset *HSPset_finalise(HSPset *hsp_set){
     }
 
 void shim_hsp_report(void){
-    if(shim_env("C4GPU_VERBOSE") && hst.sets)
+    if(shim_has(C4GPU_VERBOSE) && hst.sets)
         g_message("c4gpu hsp: %ld word hits of %ld HSP sets extended in %ld device batch(es) (%.0f ms incl. flattening and "
                   "replay), %ld HSPs passed their horizon, %ld seeds dropped at masked ends, %ld checked against the reference",
                   hst.seeds, hst.sets, hst.flushes, hst.device_ms, hst.stored, hst.dropped, hst.checked);

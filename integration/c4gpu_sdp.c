@@ -54,8 +54,8 @@ static gdouble sdp_budget_bytes(void){
     if(budget <= 0.0){
         int64_t mem = 0;
         register c4gpu_ctx *ctx = shim_get_ctx();
-        if(shim_env("C4GPU_SDP_GB"))
-            budget = atof(shim_env("C4GPU_SDP_GB")) * 1e9;
+        if(shim_has(C4GPU_SDP_GB))
+            budget = shim_real(C4GPU_SDP_GB, 0.0) * 1e9;
         else if(ctx && (c4gpu_ctx_device_info(ctx, NULL, 0, NULL, &mem) == 0) && (mem > 0))
             budget = MIN(0.8 * (gdouble)mem, 120e9);
         else
@@ -71,50 +71,40 @@ static struct { long pairs, served_pairs, alignments, flushes, async_flushes; do
  * C4GPU_CODON_SDP=1 for coding2coding (the seeded flavour), C4GPU_CODING2GENOME_SDP=1 for coding2genome (the boundary
  * flavour).  Either switch means its own family alone.  The answer is kept per SDP object: the tables do not depend on the
  * pair. */
-static gboolean sdp_coding2genome_on(void){
-    return shim_env("C4GPU_CODING2GENOME_SDP") && atoi(shim_env("C4GPU_CODING2GENOME_SDP"));
-    }
-/* the seam's flattening: with coding2genome's switch the split-codon calcs of a DNA query pass */
-static gboolean sdp_flatten(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out){
-    return sdp_coding2genome_on() ? shim_flatten_split_codon(m, ud, out) : shim_flatten_any(m, ud, out, FALSE);
+/* the seam's flattening: with coding2genome's switch, this seam's or the exhaustive seam's, the split-codon calcs of a DNA
+ * query pass (c4gpu_switches.h) */
+static guint sdp_flatten_flags(void){
+    return (shim_is(C4GPU_CODING2GENOME, 1) || shim_nonzero(C4GPU_CODING2GENOME_SDP)) ? SHIM_FLATTEN_SPLIT_CODON : 0;
     }
 
 static gboolean sdp_wide_model_served(GAM *gam, Comparison *comparison){
-    static GHashTable *known = NULL;               /* SDP* -> 1 (no) or 2 (yes) */
-    static const struct { const char *name, *env; } wide[2] = {
-        {"coding2coding", "C4GPU_CODON_SDP"}, {"coding2genome", "C4GPU_CODING2GENOME_SDP"}};
-    register gint answer, w;
+    static GHashTable *known = NULL;               /* SDP* -> no / yes */
+    static const struct { const char *name; ShimSwitchKey key; } wide[2] = {
+        {"coding2coding", C4GPU_CODON_SDP}, {"coding2genome", C4GPU_CODING2GENOME_SDP}};
+    register gint answer, w, family;
+    register gboolean ok = FALSE;
     register gpointer ud;
-    gboolean asked = FALSE;
     c4gpu_model fm, served;
     c4gpu_params params;
-    for(w = 0; w < 2; w++)
-        if(shim_env(wide[w].env) && atoi(shim_env(wide[w].env)))
-            asked = TRUE;
-    if(!asked)
+    if((!shim_nonzero(wide[0].key)) && (!shim_nonzero(wide[1].key)))
         return FALSE;
-    if(!known)
-        known = g_hash_table_new(g_direct_hash, g_direct_equal);
-    if((answer = GPOINTER_TO_INT(g_hash_table_lookup(known, gam->sdp))))
-        return answer == 2;
+    if((answer = shim_memo_get(&known, gam->sdp)))
+        return answer == SHIM_MEMO_YES;
     ud = Model_Type_create_data(gam->gas->type, comparison->query, comparison->target);
-    answer = 1;
-    if(sdp_flatten(gam->sdp->model, ud, &fm)){
+    if((family = shim_model_family(gam->sdp->model, ud, sdp_flatten_flags(), &fm)) >= 0){
         shim_params(ud, &params);
         for(w = 0; w < 2; w++)
-            if(shim_env(wide[w].env) && atoi(shim_env(wide[w].env))
+            if(shim_nonzero(wide[w].key)
             && (c4gpu_model_get(wide[w].name, C4GPU_ALPHABET_DNA, C4GPU_ALPHABET_DNA, &params, &served) == 0)
-            && (c4gpu_model_device_family(&fm) >= 0)
-            && (c4gpu_model_device_family(&fm) == c4gpu_model_device_family(&served)))
-                answer = 2;
+            && (family == c4gpu_model_device_family(&served)))
+                ok = TRUE;
         }
     Model_Type_destroy_data(gam->gas->type, ud);
-    g_hash_table_insert(known, gam->sdp, GINT_TO_POINTER(answer));
-    return answer == 2;
+    return shim_memo_put(&known, gam->sdp, ok);
     }
 
 static gboolean sdp_eligible(GAM *gam, Comparison *comparison){
-    if((shim_batch_size() <= 0) || shim_env("C4GPU_SDP_OFF") || sdp_cur)
+    if((shim_batch_size() <= 0) || shim_has(C4GPU_SDP_OFF) || sdp_cur)
         return FALSE;
     if((!gam->gas->use_gapped_extension) || (!gam->sdp))
         return FALSE;
@@ -129,7 +119,7 @@ static gboolean sdp_eligible(GAM *gam, Comparison *comparison){
         return FALSE;
     if(Comparison_Param_get_HSPSet_Argument_Set(comparison->param)->geneseed_threshold)
         return FALSE;
-    if((!shim_env("C4GPU_SDP_HOST")) && (!shim_ctx_nowait()))
+    if((!shim_has(C4GPU_SDP_HOST)) && (!shim_ctx_nowait()))
         return FALSE;
     return TRUE;
     }
@@ -239,10 +229,10 @@ static void sdp_ctx2_open(void){               /* (under sdp_ctx2_lock) */
         c4gpu_ctx_destroy(sdp_ctx2);
         sdp_ctx2 = NULL;
         }
-    if(sdp_ctx2 && (!(shim_env("C4GPU_SDP_RESERVE") && (atof(shim_env("C4GPU_SDP_RESERVE")) <= 0.0)))
+    if(sdp_ctx2 && (!(shim_has(C4GPU_SDP_RESERVE) && (shim_real(C4GPU_SDP_RESERVE, 0.0) <= 0.0)))
     && (c4gpu_ctx_device_info(sdp_ctx2, NULL, 0, NULL, &mem) == 0)){
         /* what a flush cut at the memory estimate asks for (config 5: 67.7 GB of a 288 GB device); C4GPU_SDP_RESERVE=<GB>, 0: none */
-        register gdouble want = shim_env("C4GPU_SDP_RESERVE") ? atof(shim_env("C4GPU_SDP_RESERVE")) * 1e9 : MIN(0.25 * (gdouble)mem, 70e9);
+        register gdouble want = shim_has(C4GPU_SDP_RESERVE) ? shim_real(C4GPU_SDP_RESERVE, 0.0) * 1e9 : MIN(0.25 * (gdouble)mem, 70e9);
         (void)c4gpu_ctx_sdp_reserve(sdp_ctx2, (int64_t)want);
         }
     return;
@@ -255,13 +245,6 @@ static gpointer sdp_reserve_run(gpointer data){
     g_mutex_unlock(&sdp_ctx2_lock);
     sdp_reserve_ms = (g_get_monotonic_time() - t0) / 1e3;
     return NULL;
-    }
-
-static gboolean sdp_async(void){
-    static gint on = -1;
-    if(on < 0)
-        on = (shim_env("C4GPU_SDP_ASYNC") && (atoi(shim_env("C4GPU_SDP_ASYNC")) == 0)) ? 0 : 1;
-    return on;
     }
 
 static SdpFlight *sdp_flight_prepare(GPtrArray *todo){
@@ -311,7 +294,7 @@ static SdpFlight *sdp_flight_prepare(GPtrArray *todo){
     f->first[n] = f->hsps->len;
     p = todo->pdata[0];
     ud = Model_Type_create_data(gam->gas->type, p->comparison->query, p->comparison->target);
-    if(f->qa && sdp_flatten(gam->sdp->model, ud, &f->fm)){
+    if(f->qa && shim_flatten(gam->sdp->model, ud, &f->fm, sdp_flatten_flags())){
         shim_params(ud, &f->params);
         f->ready = TRUE;
         }
@@ -420,7 +403,7 @@ static void sdp_flush_pending(gboolean async){
         sdp_pending_bytes = 0.0;
         sst.flushes++;
         shim_mark("sdp flush: batch");
-        if(shim_env("C4GPU_SDP_HOST")){
+        if(shim_has(C4GPU_SDP_HOST)){
             register guint i;
             gint64 t0 = g_get_monotonic_time(), t1;
             if(sdp_in_flight){
@@ -439,7 +422,7 @@ static void sdp_flush_pending(gboolean async){
         f = sdp_flight_prepare(todo);
         }
     /* (the last flush of a run that already has the side context goes there too: its arena is waiting) */
-    if(f && sdp_async() && (async || sdp_in_flight || sdp_reserve_thread || sst.async_flushes)){
+    if(f && shim_async(C4GPU_SDP_ASYNC) && (async || sdp_in_flight || sdp_reserve_thread || sst.async_flushes)){
         /* its device part starts now; the flight before it (if any) is landed -- joined, replayed -- beside it.  The two
          * never share the device thread's context: the one before ran on sdp_ctx2 as well, and has to be JOINED first */
         if(sdp_in_flight && sdp_in_flight->thread){
@@ -515,7 +498,7 @@ gboolean shim_sdp_collect(GAM *gam, Comparison *comparison){
         g_array_free(hsps, TRUE);
     }
     sdp_pending_bytes += 20.0 * (comparison->query->len + comparison->target->len);
-    if(sdp_async() && (!sdp_reserve_thread) && (!sdp_ctx2) && (sdp_pending_bytes > 8e9) && (!shim_env("C4GPU_SDP_HOST")))
+    if(shim_async(C4GPU_SDP_ASYNC) && (!sdp_reserve_thread) && (!sdp_ctx2) && (sdp_pending_bytes > 8e9) && (!shim_has(C4GPU_SDP_HOST)))
         sdp_reserve_thread = g_thread_new("c4gpu-sdp-arena", sdp_reserve_run, NULL);
     if(((gint)sdp_pending->len >= shim_batch_size())
     || (sdp_pending_bytes > sdp_budget_bytes()))
@@ -555,7 +538,7 @@ Alignment *SDP_Pair_next_path(SDP_Pair *sdp_pair, C4_Score threshold){
     }
 
 void shim_sdp_report(void){
-    if(shim_env("C4GPU_VERBOSE") && sst.pairs)
+    if(shim_has(C4GPU_VERBOSE) && sst.pairs)
         g_message("c4gpu sdp: %ld pairs in %ld flush(es): %ld served from device batches (%ld alignments); batches %.0f ms, "
                   "replay %.0f ms; %ld flush(es) beside the main thread, which waited %.0f ms for them (their context and arena were "
                   "ready after %.0f ms on a thread of their own)", sst.pairs, sst.flushes,

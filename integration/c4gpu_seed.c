@@ -140,12 +140,12 @@ static gpointer seed_read_slice_thread(gpointer data){
     return NULL;
     }
 static void seed_read_words(ShimSeedTab *st, FSM *f, GArray *words){
-    register gint n_threads = shim_env("C4GPU_SEED_THREADS") ? atoi(shim_env("C4GPU_SEED_THREADS")) : (gint)MIN(8, g_get_num_processors());
+    register gint n_threads = shim_num(C4GPU_SEED_THREADS, (gint)MIN(8, g_get_num_processors()));
     register gint t;
     register guint k;
     ShimWordSlice *sl;
     GThread **th;
-    if((n_threads < 2) || (words->len < (shim_env("C4GPU_SEED_THREADS") ? (guint)n_threads : 4096u))){     /* (asked for: any size) */
+    if((n_threads < 2) || (words->len < (shim_has(C4GPU_SEED_THREADS) ? (guint)n_threads : 4096u))){     /* (asked for: any size) */
         seed_read_slice(st, f, (ShimTrieItem*)words->data, words->len);
         return;
         }
@@ -235,7 +235,7 @@ static gboolean seed_worth_it(ShimSeedTab *st, Sequence *target){
     register Seeder *seeder = st->seeder;
     register gdouble nodes = seeder->seeder_fsm ? (gdouble)seeder->seeder_fsm->fsm->chunk_count
                                                 : (gdouble)seeder->seeder_vfsm->vfsm->lrw / 64.0;
-    register gdouble factor = shim_env("C4GPU_SEED_FACTOR") ? atof(shim_env("C4GPU_SEED_FACTOR")) : 4.0;
+    register gdouble factor = shim_real(C4GPU_SEED_FACTOR, 4.0);
     return (gdouble)(st->walked + target->len) >= factor * nodes;
     }
 
@@ -263,7 +263,7 @@ static ShimSeedTab *seed_state(Seeder *seeder){
 static gboolean seed_build_wanted(ShimSeedTab *st){
     register Seeder *seeder = st->seeder;
     register guint k;
-    if((!shim_env("C4GPU_SEED_BUILD")) || (!atoi(shim_env("C4GPU_SEED_BUILD"))) || shim_env("C4GPU_SEED_HOST"))
+    if((!shim_nonzero(C4GPU_SEED_BUILD)) || shim_has(C4GPU_SEED_HOST))
         return FALSE;
     if(seeder->codon_loader || seeder->saturate_threshold || (seeder->sas->word_jump != 1)
     || ((seeder->dna_loader ? 1 : 0) + (seeder->protein_loader ? 1 : 0) != 1))
@@ -431,7 +431,7 @@ static gboolean seed_build(ShimSeedTab *st){
             shim_mark("  word table built on the device");
             if(!seeder->seeder_fsm)
                 seeder->is_prepared = TRUE;
-            if(!shim_env("C4GPU_SEED_BUILD_CHECK")){
+            if(!shim_has(C4GPU_SEED_BUILD_CHECK)){
                 st->usable = TRUE;
                 sdst.words += st->codes->len; sdst.emits += st->emits->len;
                 sdst.table_ms += (g_get_monotonic_time() - t_begin) / 1e3;
@@ -459,7 +459,7 @@ static gboolean seed_build(ShimSeedTab *st){
          * first asked (seeder.c:865) -- that is only where a scan could not be served.  The failure links are of no use to the
          * word table, and compiling a 256-protein seeder's automaton took as long as reading its words (C4GPU_SEED_COMPILE=1:
          * compile here, as rounds 3-4 did) */
-        if((!f->is_compiled) && shim_env("C4GPU_SEED_COMPILE")){
+        if((!f->is_compiled) && shim_has(C4GPU_SEED_COMPILE)){
             FSM_compile(f);
             seeder->is_prepared = TRUE;
             shim_mark("  automaton compiled");
@@ -495,7 +495,7 @@ static gboolean seed_build(ShimSeedTab *st){
         seed_build_check(st, b_codes, b_first, b_emits);
         g_array_free(st->codes, TRUE); g_array_free(st->first, TRUE); g_array_free(st->emits, TRUE);
         st->codes = b_codes; st->first = b_first; st->emits = b_emits;
-    } else if(shim_env("C4GPU_SEED_HOST")){
+    } else if(shim_has(C4GPU_SEED_HOST)){
         st->host_index = g_hash_table_new(g_int64_hash, g_int64_equal);
         for(i = 0; i < (gint)st->codes->len; i++)
             g_hash_table_insert(st->host_index, &g_array_index(st->codes, guint64, i), GINT_TO_POINTER(i + 1));
@@ -613,26 +613,9 @@ static void seed_deliver_frame(ShimSeedTab *st, Sequence *target, ShimFrameHits 
     return;
     }
 
-/* ---- C4GPU_SEED_FUSED: scan to stored HSPs in one call ---- */
-
-static gint seed_match_kind(HSP_Param *param){
-    switch(param->match->type){
-        case Match_Type_DNA2DNA: return C4GPU_MATCH_DNA2DNA;
-        case Match_Type_PROTEIN2PROTEIN: return C4GPU_MATCH_PROTEIN2PROTEIN;
-        case Match_Type_PROTEIN2DNA: return C4GPU_MATCH_PROTEIN2DNA;
-        case Match_Type_CODON2CODON: return shim_codon_seed() ? C4GPU_MATCH_CODON2CODON : -1;
-        default: return -1;
-        }
-    }
-
-/* C4GPU_SEED_FUSED_OPT=1 (opt-in, beside C4GPU_SEED_FUSED=1): the route also takes soft-masked alphabets and --seedrepeat > 1
+/* ---- C4GPU_SEED_FUSED: scan to stored HSPs in one call ----
+ * C4GPU_SEED_FUSED_OPT=1 (opt-in, beside it): the route also takes soft-masked alphabets and --seedrepeat > 1
  * (c4gpu_seed_extend_opt); without it such runs keep the scan and extension calls, as they did before that call existed */
-static gboolean seed_fused_opt(void){
-    static gint on = -1;
-    if(on < 0)
-        on = (shim_env("C4GPU_SEED_FUSED_OPT") && atoi(shim_env("C4GPU_SEED_FUSED_OPT"))) ? 1 : 0;
-    return on ? TRUE : FALSE;
-    }
 
 /* once per table: one loader behind every emission, its HSP_Param one the seeding seam takes (hsp_eligible, c4gpu_hsp.c) */
 static void seed_fused_look(ShimSeedTab *st){
@@ -650,12 +633,12 @@ static void seed_fused_look(ShimSeedTab *st){
             return;
         loader = e->loader;
         }
-    if((!loader->hsp_param->use_horizon) || (seed_match_kind(loader->hsp_param) < 0))
+    if((!loader->hsp_param->use_horizon) || (shim_match_kind(loader->hsp_param->match->type, FALSE) < 0))
         return;
     /* --seedrepeat > 1: only where every seed has a horizon entry -- equal advances; protein against DNA keeps the other route
      * (c4gpu_seed_extend_opt refuses it: the reference leaves its horizon array there) */
     if((loader->hsp_param->seed_repeat > 1)
-    && ((!seed_fused_opt()) || (loader->hsp_param->match->query->advance != loader->hsp_param->match->target->advance)))
+    && ((!shim_nonzero(C4GPU_SEED_FUSED_OPT)) || (loader->hsp_param->match->query->advance != loader->hsp_param->match->target->advance)))
         return;
     codon = (loader->hsp_param->match->type == Match_Type_CODON2CODON);
     index = g_hash_table_new(g_direct_hash, g_direct_equal);
@@ -665,7 +648,7 @@ static void seed_fused_look(ShimSeedTab *st){
         g_hash_table_insert(index, query_info, GINT_TO_POINTER(k + 1));
         st->fused_query[k] = Sequence_get_str(query_info->query);
         /* (an annotated query of a codon loader: its sets keep the reference's function, hsp_match_kind in c4gpu_hsp.c) */
-        if((codon && query_info->query->annotation) || (query_info->query->alphabet->is_soft_masked && !seed_fused_opt()))
+        if((codon && query_info->query->annotation) || (query_info->query->alphabet->is_soft_masked && !shim_nonzero(C4GPU_SEED_FUSED_OPT)))
             loader = NULL;
         }
     st->fused_emits = g_new(c4gpu_seed_emit, st->emits->len);
@@ -683,16 +666,12 @@ static void seed_fused_look(ShimSeedTab *st){
     }
 
 static gboolean seed_fused_wanted(ShimSeedTab *st, Sequence *target){
-    static gint on = -1;
-    if(on < 0)
-        on = (shim_env("C4GPU_SEED_FUSED") && atoi(shim_env("C4GPU_SEED_FUSED")) && (!shim_env("C4GPU_SEED_CHECK"))
-              && (!shim_env("C4GPU_HSP_CHECK")) && (!shim_env("C4GPU_HSP_OFF"))) ? 1 : 0;
-    if(!on)
+    if((!shim_nonzero(C4GPU_SEED_FUSED)) || shim_has(C4GPU_SEED_CHECK) || shim_has(C4GPU_HSP_CHECK) || shim_has(C4GPU_HSP_OFF))
         return FALSE;
     if(!st->fused_looked)
         seed_fused_look(st);
     /* (a soft-masked target with the second switch: c4gpu_seed_extend_opt takes the alphabets' flags) */
-    return st->fused_loader && (seed_fused_opt() || !target->alphabet->is_soft_masked);
+    return st->fused_loader && (shim_nonzero(C4GPU_SEED_FUSED_OPT) || !target->alphabet->is_soft_masked);
     }
 
 /* the kept list on the device: one c4gpu_seed_extend_opt call.  The pairs hand the residues over with their case
@@ -725,7 +704,7 @@ static gboolean seed_fused_device(ShimSeedTab *st, Sequence *target, gchar *tstr
         cap += n_sym[i] / 64;
     for(;;){
         *kept = g_new(c4gpu_seed_hsp, cap + 1);
-        if(c4gpu_seed_extend_opt(shim_get_ctx(), st->tab, &params, seed_match_kind(param), pairs, n_pairs,
+        if(c4gpu_seed_extend_opt(shim_get_ctx(), st->tab, &params, shim_match_kind(param->match->type, FALSE), pairs, n_pairs,
                                  (const uint8_t *const *)sym, n_sym, n_strs, translated ? 3 : 1, frame_offset,
                                  st->fused_loader->tpos_modifier, param->seedlen, param->dropoff, param->threshold,
                                  mask_query, mask_target, param->seed_repeat, *kept, cap, stats) != 0)
@@ -920,13 +899,11 @@ void Seeder_add_target(Seeder *seeder, Sequence *target){
     gint str_frame[3], n_strs = 0;
     gint n_frames = 0;
     gboolean ok = TRUE, fused = FALSE;
-    static gint off = -1;
-    if(off < 0)
-        off = (shim_env("C4GPU_SEED_OFF") || (shim_batch_size() <= 0)) ? 1 : 0;
+    register gboolean off = shim_has(C4GPU_SEED_OFF) || (shim_batch_size() <= 0);
     shim_mark("Seeder_add_target");
     /* a translated query (codon2codon: match advance 3 on the query) has a word list per query frame, all in one automaton, its
      * seeds' query positions already nucleotide positions (seeder.c:540-545): the reference's walk unless C4GPU_CODON_SEED=1 */
-    if((!off) && ((match->query->advance == 1) || shim_codon_seed()) && (shim_env("C4GPU_SEED_HOST") || shim_ctx_nowait())){
+    if((!off) && ((match->query->advance == 1) || shim_nonzero(C4GPU_CODON_SEED)) && (shim_has(C4GPU_SEED_HOST) || shim_ctx_nowait())){
         st = seed_state(seeder);
         if(st->hopeless)
             st = NULL;
@@ -946,7 +923,7 @@ void Seeder_add_target(Seeder *seeder, Sequence *target){
         Seeder_add_target_cpu(seeder, target);
         return;
         }
-    if(shim_env("C4GPU_SEED_CHECK")){
+    if(shim_has(C4GPU_SEED_CHECK)){
         /* the reference's own walk first, its seeds written down instead of extended (no set becomes non-empty, so its
          * report loop finds nothing to report) */
         theirs = seed_record = g_array_new(FALSE, FALSE, sizeof(ShimSeedRec));
@@ -1054,18 +1031,18 @@ void Seeder_destroy(Seeder *seeder){
     }
 
 void shim_seed_report(void){
-    if(shim_env("C4GPU_VERBOSE") && sdst.cpu_targets)
+    if(shim_has(C4GPU_VERBOSE) && sdst.cpu_targets)
         g_message("c4gpu seed: %ld targets left to the reference's walk (their seeder's word table was not worth reading yet)",
                   sdst.cpu_targets);
-    if(shim_env("C4GPU_VERBOSE") && sdst.targets)
+    if(shim_has(C4GPU_VERBOSE) && sdst.targets)
         g_message("c4gpu seed: %ld targets walked in %ld device scans (%ld symbols): %ld word hits; scans %.0f ms, "
                   "delivery %.0f ms, word tables (%ld words, %ld emissions) %.0f ms%s", sdst.targets, sdst.scans, sdst.symbols,
                   sdst.hits, sdst.scan_ms, sdst.host_ms, sdst.words, sdst.emits, sdst.table_ms,
                   sdst.checked ? "; every seed equal to the reference's own walk" : "");
-    if(shim_env("C4GPU_VERBOSE") && (sdst.read || sdst.built))
+    if(shim_has(C4GPU_VERBOSE) && (sdst.read || sdst.built))
         g_message("c4gpu seed: word tables: %ld read off the automaton, %ld built on the device (c4gpu_wordtab_build %.0f ms)",
                   sdst.read, sdst.built, sdst.build_ms);
-    if(shim_env("C4GPU_VERBOSE") && shim_env("C4GPU_SEED_FUSED") && atoi(shim_env("C4GPU_SEED_FUSED")))
+    if(shim_has(C4GPU_VERBOSE) && shim_nonzero(C4GPU_SEED_FUSED))
         g_message("c4gpu seed fused: %ld targets through c4gpu_seed_extend: %ld word hits, %ld extensions, %ld HSPs kept "
                   "(%.0f ms with delivery)", sdst.fused_targets, sdst.fused_hits, sdst.fused_extended, sdst.fused_kept, sdst.fused_ms);
     return;

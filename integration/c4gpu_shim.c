@@ -86,47 +86,36 @@ static void shim_fault(int sig){
  * getenv walks `environ` without a lock, and the HIP / HSA start-up on the device thread ADDS variables (setenv moves the array):
  * the main thread's look-ups in the seams' hot paths (one per seeded HSP) then ran into freed memory -- SIGSEGV inside getenv in
  * 3 % of the 0.3 s heuristic runs that overlap the device's start-up (tools/gpu_small_work_stress.sh: 9 of 300 before, 0 after). */
-extern char **environ;
-static struct { gchar *name, *value; } *shim_env_copy = NULL;
-static gint shim_env_n = 0;
-const gchar *shim_env(const gchar *name){
-    register gint i;
-    for(i = 0; i < shim_env_n; i++)
-        if(!strcmp(shim_env_copy[i].name, name))
-            return shim_env_copy[i].value;
-    return NULL;
-    }
-static void shim_env_snapshot(void){
-    register char **e;
-    register gint n = 0;
-    for(e = environ; e && *e; e++)
-        if(!strncmp(*e, "C4GPU_", 6))
-            n++;
-    shim_env_copy = calloc(n + 1, sizeof(*shim_env_copy));
-    for(e = environ; e && *e; e++){
-        register const char *eq = strchr(*e, '=');
-        if(strncmp(*e, "C4GPU_", 6) || !eq)
-            continue;
-        shim_env_copy[shim_env_n].name = strndup(*e, eq - *e);
-        shim_env_copy[shim_env_n].value = strdup(eq + 1);
-        shim_env_n++;
+ShimSwitch shim_switch[SHIM_N_SWITCHES];           /* the keys and their accessors: c4gpu_switches.h */
+static void shim_env_snapshot(void){               /* THE place where the shim reads its environment */
+    static const gchar *const names[SHIM_N_SWITCHES] = {
+#define X(name) #name,
+        SHIM_SWITCHES(X)
+#undef X
+        };
+    register gint k;
+    for(k = 0; k < SHIM_N_SWITCHES; k++){
+        register const gchar *v = getenv(names[k]);
+        register ShimSwitch *sw = &shim_switch[k];
+        if((sw->set = (v != NULL))){
+            sw->text = strdup(v);
+            sw->value = atoi(v);
+            sw->real = atof(v);
+            }
         }
     return;
     }
 static void __attribute__((constructor)) shim_clock_start(void){
     shim_t0 = g_get_monotonic_time();
     shim_env_snapshot();
-    if(shim_env("C4GPU_SEGV_TRACE")){
+    if(shim_has(C4GPU_SEGV_TRACE)){
         signal(SIGSEGV, shim_fault);
         signal(SIGABRT, shim_fault);
         signal(SIGBUS, shim_fault);
         }
     }
 void shim_mark(const gchar *what){          /* C4GPU_TRACE: where the wall time of a run goes */
-    static gint on = -1;
-    if(on < 0)
-        on = shim_env("C4GPU_TRACE") ? 1 : 0;
-    if(on)
+    if(shim_has(C4GPU_TRACE))
         g_printerr("c4gpu mark: %8.1f ms  %s\n", (g_get_monotonic_time() - shim_t0) / 1e3, what);
     return;
     }
@@ -145,13 +134,13 @@ static gchar *shim_ctx_error = NULL;
  * reference's own objects (general/argument.c's error handler among them), which the Makefile points at shim_exit with
  * objcopy --redefine-sym.  Then the ordinary exit(), handlers and all.  Rounds 3-4 left with _exit here (stdio flushed first)
  * because one short run in about two hundred ended with SIGSEGV after its complete output; round 5 found the cause elsewhere --
- * getenv on the main thread racing with the setenv calls of the HIP start-up on the device thread (shim_env above) -- and with
+ * getenv on the main thread racing with the setenv calls of the HIP start-up on the device thread (shim_env_snapshot above) -- and with
  * that gone the ordinary exit ended 1 500 of 1 500 short runs cleanly (profiles/r05_small_work_stress_exit.log), so _exit is now
  * the exception: C4GPU_FAST_EXIT=1 asks for it, and a way out that is taken while a flush thread is still on the device (an
  * error exit in the middle of a run) takes it too. */
 static gboolean shim_joined = FALSE;
 static gboolean shim_fast_exit(void){
-    register const gchar *e = shim_env("C4GPU_FAST_EXIT");
+    register const gchar *e = shim_text(C4GPU_FAST_EXIT);
     return shim_ctx_thread && e && (e[0] == '1');
     }
 static gboolean shim_flush_threads_alive(void);
@@ -187,7 +176,7 @@ static gpointer shim_ctx_open(gpointer data){
         ctx = c4gpu_ctx_create(shim_device_ordinal());
     /* C4GPU_OWN_STREAM=1: a stream of its own instead of the default one (tried while looking for what held the word scans up
      * beside an SDP flight, profiles/r05_c5_cold.md: it was not the default stream, and the default stays) */
-    if(ctx && shim_env("C4GPU_OWN_STREAM") && (c4gpu_ctx_own_stream(ctx) != 0))
+    if(ctx && shim_has(C4GPU_OWN_STREAM) && (c4gpu_ctx_own_stream(ctx) != 0))
         g_warning("c4gpu: %s -- launching in the default stream", c4gpu_last_error());
     shim_t_ready = g_get_monotonic_time();
     g_mutex_lock(&shim_ctx_lock);
@@ -199,7 +188,7 @@ static gpointer shim_ctx_open(gpointer data){
     shim_ctx_ready = TRUE;
     g_cond_broadcast(&shim_ctx_cond);
     g_mutex_unlock(&shim_ctx_lock);
-    if(ctx && !shim_env("C4GPU_NO_WARM"))
+    if(ctx && !shim_has(C4GPU_NO_WARM))
         c4gpu_ctx_warm(ctx);
     shim_t_warm = g_get_monotonic_time();
     return NULL;
@@ -209,8 +198,8 @@ static void shim_start_ctx(void){
     if(shim_tried)
         return;
     shim_tried = TRUE;
-    shim_verbose = (shim_env("C4GPU_VERBOSE") != NULL);
-    if((!shim_args.use_gpu) || shim_env("C4GPU_DISABLE"))
+    shim_verbose = shim_has(C4GPU_VERBOSE);
+    if((!shim_args.use_gpu) || shim_has(C4GPU_DISABLE))
         return;
     g_mutex_lock(&shim_ctx_lock);
     shim_ctx_thread = g_thread_new("c4gpu-ctx", shim_ctx_open, NULL);
@@ -231,7 +220,7 @@ int main(int argc, char **argv){
     }
 
 gint shim_device_ordinal(void){
-    return shim_env("C4GPU_DEVICE") ? atoi(shim_env("C4GPU_DEVICE")) : shim_args.device;
+    return shim_num(C4GPU_DEVICE, shim_args.device);
     }
 
 c4gpu_ctx *shim_get_ctx(void){
@@ -266,7 +255,7 @@ c4gpu_ctx *shim_get_ctx(void){
 c4gpu_ctx *shim_ctx_nowait(void){
     register gboolean ready;
     shim_start_ctx();
-    if((!shim_ctx_thread) || shim_env("C4GPU_WAIT"))
+    if((!shim_ctx_thread) || shim_has(C4GPU_WAIT))
         return shim_get_ctx();
     g_mutex_lock(&shim_ctx_lock);
     ready = shim_ctx_ready;
@@ -276,23 +265,15 @@ c4gpu_ctx *shim_ctx_nowait(void){
 
 /* ---- C4_Model (closed) -> c4gpu_model ------------------------------------------------------------- */
 
-/* --annotation (match.c:276-281: no 1:1 DNA match inside a DNA query's CDS): the Optimal seams -- the per-call shim and the
- * exhaustive batches -- hand the annotation to the library (c4gpu_batch_set_annotation) and set this around their flattening;
- * the other seams (BSDP's sub-DPs, SDP, seeding: their kernels read their own tables) still leave such runs to the
- * reference's functions. */
-static __thread gboolean shim_annotation_ok = FALSE;
-
-/* Set around the flattening of a seam that has its own switch for split codons against a translated DNA query (the SDP seam,
- * C4GPU_CODING2GENOME_SDP=1: shim_flatten_split_codon) */
-static __thread gboolean shim_split_codon_ok = FALSE;
-
-/* C4GPU_CODING2GENOME=1: serve coding2genome's exhaustive runs from its device family (off unless asked) */
-static gboolean shim_coding2genome_on(void){
-    register const gchar *e = shim_env("C4GPU_CODING2GENOME");
-    return e && (atoi(e) == 1);
+/* The flags of the Optimal seams, the per-call shim and the exhaustive batches.  --annotation (match.c:276-281: no 1:1 DNA match
+ * inside a DNA query's CDS): they hand the annotation to the library (c4gpu_batch_set_annotation); the other seams (BSDP's
+ * sub-DPs, SDP, seeding: their kernels read their own tables) still leave such runs to the reference's functions.
+ * C4GPU_CODING2GENOME=1: coding2genome's exhaustive runs are served from its device family (off unless asked). */
+static guint shim_optimal_flags(void){
+    return SHIM_FLATTEN_ANNOTATED | (shim_is(C4GPU_CODING2GENOME, 1) ? SHIM_FLATTEN_SPLIT_CODON : 0);
     }
 
-gboolean shim_flatten_any(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out, gboolean allow_span){
+gboolean shim_flatten(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out, guint flags){
     register guint i, j;
     memset(out, 0, sizeof(*out));
     if((m->state_list->len > C4GPU_MAX_STATES) || (m->transition_list->len > C4GPU_MAX_TRANSITIONS)
@@ -312,7 +293,7 @@ gboolean shim_flatten_any(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out, gboo
     out->total_shadow_designations = m->total_shadow_designations;
     out->query_alphabet = (ud->query->alphabet->type == Alphabet_Type_PROTEIN);
     out->target_alphabet = (ud->target->alphabet->type == Alphabet_Type_PROTEIN);
-    if((m->start_state->cell_start_func || m->end_state->cell_end_func) && !allow_span)
+    if((m->start_state->cell_start_func || m->end_state->cell_end_func) && !(flags & SHIM_FLATTEN_SPANS))
         return FALSE;                                /* BSDP span models: only with their matrices (c4gpu_bsdp.c) */
     for(i = 0; i < m->state_list->len; i++){
         C4_State *s = m->state_list->pdata[i];
@@ -344,7 +325,7 @@ gboolean shim_flatten_any(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out, gboo
             else if(out->query_alphabet && out->target_alphabet) o->kind = C4GPU_CALC_MATCH_PROTEIN;
             else if(!out->query_alphabet && !out->target_alphabet) o->kind = C4GPU_CALC_MATCH_DNA;
             else return FALSE;
-            if(ud->query->annotation && (!shim_annotation_ok)) return FALSE; /* cds veto, match.c:276-281 */
+            if(ud->query->annotation && !(flags & SHIM_FLATTEN_ANNOTATED)) return FALSE; /* cds veto, match.c:276-281 */
         } else if((!strcmp(c->name, "gap open")) || (!strcmp(c->name, "gap extend"))
                || (!strcmp(c->name, "frameshift")) || (!strcmp(c->name, "ner open"))){
             /* "ner open" reads its penalty through the user data: NER_Data begins with Affine_Data, which begins with
@@ -362,10 +343,10 @@ gboolean shim_flatten_any(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out, gboo
         } else if(!strncmp(c->name, "5'ss reverse", 12)){
             o->kind = C4GPU_CALC_SPLICE_POST; o->param = C4GPU_SS5_REVERSE;
         } else if((!strncmp(c->name, "phase1post to dst", 17)) || (!strncmp(c->name, "phase2post to dst", 17))){
-            /* split codons against a translated DNA query (coding2genome and what is derived from it): the device family is
-             * opt-in, C4GPU_CODING2GENOME=1 (the SDP seam: its own switch); without it every call of such a model stays with the
-             * reference */
-            if(shim_model_has_wide_query_advance(m) && (!shim_coding2genome_on()) && (!shim_split_codon_ok))
+            /* split codons against a translated DNA query (coding2genome and what is derived from it): the device families are
+             * opt-in, each seam by its own switch (c4gpu_switches.h); without the flag every call of such a model stays with
+             * the reference */
+            if(shim_model_has_wide_query_advance(m) && !(flags & SHIM_FLATTEN_SPLIT_CODON))
                 return FALSE;
             o->kind = C4GPU_CALC_PHASE_POST; o->param = (c->name[5] == '1') ? 1 : 2;
         } else {
@@ -420,35 +401,45 @@ gboolean shim_model_has_query_span(C4_Model *m){
     return FALSE;
     }
 
-gboolean shim_flatten_split_codon_any(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out, gboolean allow_span){
-    register gboolean ok;
-    shim_split_codon_ok = TRUE;
-    ok = shim_flatten_any(m, ud, out, allow_span);
-    shim_split_codon_ok = FALSE;
-    return ok;
+gint shim_model_family(C4_Model *m, Ungapped_Data *ud, guint flags, c4gpu_model *out){
+    return shim_flatten(m, ud, out, flags) ? c4gpu_model_device_family(out) : -1;
     }
 
-gboolean shim_flatten_split_codon(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out){
-    return shim_flatten_split_codon_any(m, ud, out, FALSE);
+gint shim_memo_get(GHashTable **memo, gconstpointer key){
+    return *memo ? GPOINTER_TO_INT(g_hash_table_lookup(*memo, key)) : SHIM_MEMO_UNKNOWN;
     }
 
-static gboolean shim_flatten(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out){
-    return shim_flatten_any(m, ud, out, FALSE);
+gboolean shim_memo_put(GHashTable **memo, gconstpointer key, gboolean yes){
+    if(!*memo)
+        *memo = g_hash_table_new(g_direct_hash, g_direct_equal);
+    g_hash_table_insert(*memo, (gpointer)key, GINT_TO_POINTER(yes ? SHIM_MEMO_YES : SHIM_MEMO_NO));
+    return yes;
     }
-/* ... for a seam that passes a query's annotation on */
-static gboolean shim_flatten_annotated(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out){
-    register gboolean ok;
-    shim_annotation_ok = TRUE;
-    ok = shim_flatten_any(m, ud, out, FALSE);
-    shim_annotation_ok = FALSE;
-    return ok;
-    }
+
 /* the annotation as the library takes it (only a DNA query's counts: match.c:277) */
 static void shim_cds(Sequence *query, int32_t *start, int32_t *length){
     *start = 0; *length = 0;
     if(query->annotation && (query->alphabet->type == Alphabet_Type_DNA)){
         *start = query->annotation->cds_start;
         *length = query->annotation->cds_length;
+        }
+    return;
+    }
+
+/* the defaults, then a Match_ArgumentSet's matrices and translation */
+static void shim_match_params(Match_ArgumentSet *mas, c4gpu_params *p){
+    register gint i, j;
+    c4gpu_params_default(p);
+    for(i = 0; i < SUBMAT_ALPHABETSIZE; i++)
+        for(j = 0; j < SUBMAT_ALPHABETSIZE; j++){
+            p->dna_submat[i][j] = mas->dna_submat->matrix[i][j];
+            p->protein_submat[i][j] = mas->protein_submat->matrix[i][j];
+            }
+    memcpy(p->submat_index, mas->dna_submat->index, 256);
+    if(mas->translate){
+        memcpy(p->nt2d, mas->translate->nt2d, 256);
+        memcpy(p->trans, mas->translate->trans, 4096);
+        memcpy(p->aa, mas->translate->aa, 40);
         }
     return;
     }
@@ -460,18 +451,7 @@ void shim_params(Ungapped_Data *ud, c4gpu_params *p){
     register Frameshift_ArgumentSet *fas = Frameshift_ArgumentSet_create(NULL);
     register gint i, j, k;
     SplicePredictor *sp[4];
-    c4gpu_params_default(p);
-    for(i = 0; i < SUBMAT_ALPHABETSIZE; i++)
-        for(j = 0; j < SUBMAT_ALPHABETSIZE; j++){
-            p->dna_submat[i][j] = ud->mas->dna_submat->matrix[i][j];
-            p->protein_submat[i][j] = ud->mas->protein_submat->matrix[i][j];
-            }
-    memcpy(p->submat_index, ud->mas->dna_submat->index, 256);
-    if(ud->mas->translate){
-        memcpy(p->nt2d, ud->mas->translate->nt2d, 256);
-        memcpy(p->trans, ud->mas->translate->trans, 4096);
-        memcpy(p->aa, ud->mas->translate->aa, 40);
-        }
+    shim_match_params(ud->mas, p);
     p->gap_open = aas->gap_open; p->gap_extend = aas->gap_extend;
     p->codon_gap_open = aas->codon_gap_open; p->codon_gap_extend = aas->codon_gap_extend;
     p->min_intron = ias->min_intron; p->max_intron = ias->max_intron;
@@ -499,21 +479,8 @@ void shim_params(Ungapped_Data *ud, c4gpu_params *p){
     }
 
 void shim_hsp_params(c4gpu_params *p){
-    register Match_ArgumentSet *mas = Match_ArgumentSet_create(NULL);
-    register gint i, j;
     memset(p, 0, sizeof(*p));
-    c4gpu_params_default(p);
-    for(i = 0; i < SUBMAT_ALPHABETSIZE; i++)
-        for(j = 0; j < SUBMAT_ALPHABETSIZE; j++){
-            p->dna_submat[i][j] = mas->dna_submat->matrix[i][j];
-            p->protein_submat[i][j] = mas->protein_submat->matrix[i][j];
-            }
-    memcpy(p->submat_index, mas->dna_submat->index, 256);
-    if(mas->translate){
-        memcpy(p->nt2d, mas->translate->nt2d, 256);
-        memcpy(p->trans, mas->translate->trans, 4096);
-        memcpy(p->aa, mas->translate->aa, 40);
-        }
+    shim_match_params(Match_ArgumentSet_create(NULL), p);
     return;
     }
 
@@ -533,13 +500,11 @@ static C4_Score shim_dp(C4_Model *model, Region *region, Viterbi_Data *vd, SubOp
     register gint i, j, k, l, cs = vd->vr->cell_size;
     register C4_Score score;
     c4gpu_subopt *blocked = NULL;
-    static gdouble min_cells = -1.0;
-    if(min_cells < 0.0)
-        min_cells = shim_env("C4GPU_MIN_CELLS") ? atof(shim_env("C4GPU_MIN_CELLS")) : 1e5;
+    register gdouble min_cells = shim_real(C4GPU_MIN_CELLS, 1e5);
     /* a single small rectangle is faster on the host than one launch + copies (a batch is another matter) */
     if(cpu_func && (((gdouble)region->query_length + 1.0) * ((gdouble)region->target_length + 1.0) < min_cells))
         return cpu_func(model, region, vd, soi, user_data);
-    if((!shim_get_ctx()) || (!shim_flatten_annotated(model, ud, &fm))){
+    if((!shim_get_ctx()) || (!shim_flatten(model, ud, &fm, shim_optimal_flags()))){
         if(!cpu_func)
             g_error("c4gpu shim: no CPU implementation to fall back to");
         return cpu_func(model, region, vd, soi, user_data);
@@ -735,11 +700,11 @@ gpointer Bootstrapper_lookup(gchar *name){
     register int mode = shim_mode_of(name);
     register Viterbi_DP_Func cpu = (Viterbi_DP_Func)Bootstrapper_lookup_cpu(name);
     /* only the Optimal (full Viterbi) functions are ours: "optimal_58_<model>_32_find_32_<mode>" */
-    if((mode < 0) || strncmp(name, "optimal_58_", 11) || shim_env("C4GPU_DISABLE") || (!shim_args.use_gpu))
+    if((mode < 0) || strncmp(name, "optimal_58_", 11) || shim_has(C4GPU_DISABLE) || (!shim_args.use_gpu))
         return (gpointer)cpu;
     /* coding2genome unless asked for: the look-up answers what the reference's own would (no compiled function in the archive:
      * Viterbi_calculate runs its interpreted loop, viterbi.c:855-859), so no call of the run comes here */
-    if((!strncmp(name, "optimal_58_coding2genome_32_", 28)) && (!shim_coding2genome_on()))
+    if((!strncmp(name, "optimal_58_coding2genome_32_", 28)) && (!shim_is(C4GPU_CODING2GENOME, 1)))
         return (gpointer)cpu;
     /* no compiled CPU function of this name (the archive was built without the model) and no device either: leave
      * the slot empty, Viterbi_calculate then runs the reference's interpreted loop (viterbi.c:855-859) */
@@ -790,16 +755,10 @@ static ShimPending *shim_replay_pair = NULL;
 static gint shim_replay_call = 0;
 
 gint shim_batch_size(void){
-    static gint size = -1;
-    if(size < 0)
-        size = shim_env("C4GPU_BATCH") ? atoi(shim_env("C4GPU_BATCH")) : shim_args.batch;
-    return size;
+    return shim_num(C4GPU_BATCH, shim_args.batch);
     }
 
 static gboolean shim_can_batch(GAM *gam, Sequence *query, Sequence *target){
-    register gpointer ud;
-    register gboolean ok;
-    c4gpu_model fm;
     if((shim_batch_size() <= 0) || (!gam->optimal) || (!shim_get_ctx()))
         return FALSE;
     if(gam->gas->refinement != GAM_Refinement_NONE)
@@ -807,24 +766,24 @@ static gboolean shim_can_batch(GAM *gam, Sequence *query, Sequence *target){
     if((gam->optimal->type & (Optimal_Type_SCORE|Optimal_Type_PATH|Optimal_Type_REDUCED_SPACE))
        != (Optimal_Type_SCORE|Optimal_Type_PATH|Optimal_Type_REDUCED_SPACE))
         return FALSE;
-    {   /* whether the model is one of the accelerated families does not depend on the pair: asked once per model (the
-         * per-pair user data the flattening reads -- Match tables, splice predictors -- are the process's static argument
-         * sets); at 4 096 pairs of a run the repeated check was 0.1 ms per pair */
-        static GAM *seen_gam = NULL;                 /* (pinned while pairs of it are pending: GAM_share below) */
-        static C4_Model *seen_model = NULL;
-        static gboolean seen_ok = FALSE;
-        static Alphabet_Type seen_q, seen_t;
-        if((seen_gam == gam) && (seen_model == gam->optimal->find_path->model) && (seen_q == query->alphabet->type)
-        && (seen_t == target->alphabet->type))
-            return seen_ok;
-        seen_gam = gam;
+    {   /* whether the model is one of the accelerated families does not depend on the pair: asked once per model and pair of
+         * alphabets (the per-pair user data the flattening reads -- Match tables, splice predictors -- are the process's
+         * static argument sets); at 4 096 pairs of a run the repeated check was 0.1 ms per pair.  The key is the GAM's own model
+         * (a GAM builds its Optimal once, from its model type), in one memo per pair of alphabets */
+        static GHashTable *memo[Alphabet_Type_UNKNOWN + 1][Alphabet_Type_UNKNOWN + 1];
+        register C4_Model *model = gam->optimal->find_path->model;
+        register GHashTable **known = &memo[query->alphabet->type][target->alphabet->type];
+        register gint answer = shim_memo_get(known, model);
+        register gpointer ud;
+        register gboolean ok;
+        c4gpu_model fm;
+        if(answer)
+            return answer == SHIM_MEMO_YES;
         ud = Model_Type_create_data(gam->gas->type, query, target);
-        ok = shim_flatten_annotated(gam->optimal->find_path->model, ud, &fm);
+        ok = shim_flatten(model, ud, &fm, shim_optimal_flags());
         Model_Type_destroy_data(gam->gas->type, ud);
-        seen_model = gam->optimal->find_path->model; seen_q = query->alphabet->type; seen_t = target->alphabet->type;
-        seen_ok = ok;
+        return shim_memo_put(known, model, ok);
         }
-    return ok;
     }
 
 /* GAM_QueryInfo_create (gam.c:466-487): the --percent threshold of a query = the best self-comparison score
@@ -888,13 +847,6 @@ static guint shim_flush_seq = 0;
 static ShimFlushJob *shim_in_flight = NULL;
 static volatile gint shim_device_busy = 0;        /* a flush thread is between taking and releasing the device */
 
-static gboolean shim_async(void){
-    static gint on = -1;
-    if(on < 0)
-        on = (shim_env("C4GPU_ASYNC") && (atoi(shim_env("C4GPU_ASYNC")) == 0)) ? 0 : 1;
-    return on;
-    }
-
 static ShimFlushJob *shim_flush_prepare(void){
     register guint i, n;
     register ShimPending *sp;
@@ -907,7 +859,7 @@ static ShimFlushJob *shim_flush_prepare(void){
     shim_pending = NULL;          /* pairs submitted from here on start a new collection */
     shim_pending_bytes = 0.0;
     job = g_new0(ShimFlushJob, 1);
-    job->slot = (shim_env("C4GPU_SLOTS") && (atoi(shim_env("C4GPU_SLOTS")) == 2)) ? (gint)(shim_flush_seq++ & 1) : 0;
+    job->slot = shim_is(C4GPU_SLOTS, 2) ? (gint)(shim_flush_seq++ & 1) : 0;
     job->t_start = g_get_monotonic_time();
     job->todo = todo;
     n = job->n = todo->len;
@@ -915,7 +867,7 @@ static ShimFlushJob *shim_flush_prepare(void){
     job->gam = sp->gam;
     job->threshold = job->gam->gas->threshold;
     job->dpmemory = job->gam->optimal->find_path->vas->traceback_memory_limit;
-    job->rounds_max = shim_env("C4GPU_BATCH_ROUNDS") ? atoi(shim_env("C4GPU_BATCH_ROUNDS")) : 4;
+    job->rounds_max = shim_num(C4GPU_BATCH_ROUNDS, 4);
     if(!job->gam->gas->use_subopt)
         job->rounds_max = 1;
     job->pair = g_new0(c4gpu_pair, n);
@@ -942,7 +894,7 @@ static ShimFlushJob *shim_flush_prepare(void){
     sp = todo->pdata[0];
     ud = Model_Type_create_data(job->gam->gas->type, sp->query, sp->target);
     memset(&job->fm, 0, sizeof(job->fm));
-    if((job->flattened = shim_flatten_annotated(job->gam->optimal->find_path->model, ud, &job->fm)))
+    if((job->flattened = shim_flatten(job->gam->optimal->find_path->model, ud, &job->fm, shim_optimal_flags())))
         shim_params(ud, &job->params);
     /* --annotation: the CDS of every annotated DNA query of the batch (c4gpu_batch_set_annotation) */
     job->cds_start = job->cds_length = NULL;
@@ -1144,7 +1096,7 @@ static void shim_flush_replay(ShimFlushJob *job){
 static void shim_flush(void){
     register ShimFlushJob *job = shim_flush_prepare();
     if(job){
-        if(shim_in_flight && shim_async())       /* the last batch goes to the device while the one before it is replayed */
+        if(shim_in_flight && shim_async(C4GPU_ASYNC))       /* the last batch goes to the device while the one before it is replayed */
             job->thread = g_thread_new("c4gpu-flush", shim_flush_device, job);
         else
             shim_flush_device(job);
@@ -1166,7 +1118,7 @@ static gboolean shim_flush_threads_alive(void){
 
 static void shim_flush_async(void){
     register ShimFlushJob *job, *before = shim_in_flight;
-    if(!shim_async()){
+    if(!shim_async(C4GPU_ASYNC)){
         shim_flush();
         return;
         }
@@ -1185,7 +1137,7 @@ static void shim_flush_async(void){
  * pair of the all-against-all run.  Every other caller (hpair.c:805, any run with -S yes) reaches the reference's function. */
 extern void SubOpt_add_alignment_cpu(SubOpt *subopt, Alignment *alignment);
 void SubOpt_add_alignment(SubOpt *subopt, Alignment *alignment){
-    if(shim_replay_pair && (!shim_replay_pair->gam->gas->use_subopt) && !shim_env("C4GPU_KEEP_SUBOPT"))
+    if(shim_replay_pair && (!shim_replay_pair->gam->gas->use_subopt) && !shim_has(C4GPU_KEEP_SUBOPT))
         return;
     SubOpt_add_alignment_cpu(subopt, alignment);
     return;
@@ -1212,15 +1164,15 @@ GAM_Result *GAM_Result_exhaustive_create(GAM *gam, Sequence *query, Sequence *ta
     /* residues + codes + 4 int32 splice arrays + tn4 per target position; flush well inside the HBM */
     shim_pending_bytes += 22.0 * target->len + 2.0 * query->len;
     if(((gint)shim_pending->len >= shim_batch_size())
-    || (shim_pending_bytes > (shim_env("C4GPU_BATCH_GB") ? atof(shim_env("C4GPU_BATCH_GB")) : 96.0) * 1e9))
+    || (shim_pending_bytes > shim_real(C4GPU_BATCH_GB, 96.0) * 1e9))
         shim_flush_async();
     /* C4GPU_EAGER=1 (off by default): also whenever the device has nothing to do and an eighth of --gpubatch (at least 256 pairs)
      * has collected, so that the first pairs of a run go to the device while the front end is still reading the rest.  Measured
      * on the 64 x 64 run (profiles/r05_dropin_c4.log): 1.71 s at best against 1.73-1.87 s without, but 2.4-2.6 s in two runs of
      * three -- the small first batch sizes the launch buffers, and the full batches behind it grow them in the middle of a run */
-    else if(shim_async() && (!g_atomic_int_get(&shim_device_busy))
+    else if(shim_async(C4GPU_ASYNC) && (!g_atomic_int_get(&shim_device_busy))
          && ((gint)shim_pending->len >= MAX(256, shim_batch_size() / 8))
-         && shim_env("C4GPU_EAGER") && (atoi(shim_env("C4GPU_EAGER")) != 0))
+         && shim_nonzero(C4GPU_EAGER))
         shim_flush_async();
     return NULL;                  /* the result is submitted by the flush, in submission order */
     }

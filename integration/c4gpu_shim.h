@@ -1,5 +1,6 @@
-/* c4gpu_shim.h — what the two files of the exonerate-gpu shim share (c4gpu_shim.c: the Viterbi plug-in table and
- * the exhaustive batching seam; c4gpu_bsdp.c: the heuristic / BSDP seam). */
+/* c4gpu_shim.h — what the five files of the exonerate-gpu shim share (c4gpu_shim.c: the Viterbi plug-in table and the exhaustive
+ * batching seam; c4gpu_bsdp.c: the heuristic / BSDP seam; c4gpu_sdp.c: the SDP seam; c4gpu_hsp.c: HSP extension; c4gpu_seed.c:
+ * the word scan).  Their switches: c4gpu_switches.h. */
 #ifndef INCLUDED_C4GPU_SHIM_H
 #define INCLUDED_C4GPU_SHIM_H
 
@@ -10,20 +11,27 @@
 #include "comparison.h"
 #include "hspset.h"
 #include "c4gpu.h"
+#include "c4gpu_switches.h"
 
 c4gpu_ctx *shim_get_ctx(void);
-const gchar *shim_env(const gchar *name);   /* a C4GPU_* variable as it was when the process started: never getenv (c4gpu_shim.c) */
 gint shim_device_ordinal(void);        /* --gpudevice / C4GPU_DEVICE: for a second context of the same device */
 c4gpu_ctx *shim_ctx_nowait(void);       /* NULL while the device is still being opened (small work does not wait) */
 void shim_mark(const gchar *what);
 gint shim_batch_size(void);
-/* closed C4_Model -> c4gpu_model; allow_span: BSDP's span models (cell_start_func / cell_end_func become matrices) */
-gboolean shim_flatten_any(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out, gboolean allow_span);
-/* ... for a seam that serves split codons against a translated DNA query (coding2genome) under a switch of its own, whatever
- * C4GPU_CODING2GENOME (the exhaustive seam's switch) says */
-gboolean shim_flatten_split_codon(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out);
-/* ... and with BSDP's span models allowed (the BSDP seam, C4GPU_CODING2GENOME_BSDP=1) */
-gboolean shim_flatten_split_codon_any(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out, gboolean allow_span);
+/* a seam's device part on a thread of its own: on unless its switch says 0 (C4GPU_ASYNC, C4GPU_SDP_ASYNC) */
+static inline gboolean shim_async(ShimSwitchKey key){ return !shim_is(key, 0); }
+/* closed C4_Model -> c4gpu_model.  What a seam lets through is its flag word, from one small function of the seam's own (the
+ * table of seam x switch -> flags: c4gpu_switches.h); the flattening reads no switch itself. */
+#define SHIM_FLATTEN_SPANS       1u    /* BSDP's span models: cell_start_func / cell_end_func become matrices (c4gpu_bsdp.c) */
+#define SHIM_FLATTEN_ANNOTATED   2u    /* the seam hands a DNA query's annotation to the library (c4gpu_batch_set_annotation) */
+#define SHIM_FLATTEN_SPLIT_CODON 4u    /* split codons against a translated DNA query (coding2genome and what is derived from it) */
+gboolean shim_flatten(C4_Model *m, Ungapped_Data *ud, c4gpu_model *out, guint flags);
+/* ... and the device family of the result, or -1 when the flattening declines (or the tables have no family) */
+gint shim_model_family(C4_Model *m, Ungapped_Data *ud, guint flags, c4gpu_model *out);
+/* "is this served", asked once per object: a pointer key -> not asked yet / no / yes (the table is made on first use) */
+enum { SHIM_MEMO_UNKNOWN = 0, SHIM_MEMO_NO, SHIM_MEMO_YES };
+gint shim_memo_get(GHashTable **memo, gconstpointer key);
+gboolean shim_memo_put(GHashTable **memo, gconstpointer key, gboolean yes);      /* returns yes */
 /* TRUE when some span of the model (C4_Model_add_span) loops on the query axis: the device SDP passes and BSDP's compiled span
  * families only know spans along the target (introns), so the heuristic seams leave such a model (ner: a span on both axes,
  * ner.c:105) to the reference's own functions */
@@ -38,7 +46,8 @@ void shim_params(Ungapped_Data *ud, c4gpu_params *p);
 void shim_hsp_params(c4gpu_params *p);
 /* c4gpu_hsp.c */
 void shim_hsp_report(void);
-gboolean shim_codon_seed(void);        /* C4GPU_CODON_SEED=1: the HSP and word-scan seams take the translated models' seeds */
+/* the device's match kind, or -1; codons: with C4GPU_CODON_SEED, and not for an annotated query (the scan seam passes FALSE) */
+gint shim_match_kind(Match_Type type, gboolean annotated_query);
 /* c4gpu_bsdp.c */
 void shim_bsdp_flush(void);
 void shim_bsdp_report(void);
